@@ -18,10 +18,15 @@ RCCL point-to-point over xGMI) runs after the timed region and is reported as "e
 --replica: weak scaling instead (every rank quantizes its own copy of the set).
 
 Clocks: the chip's clocks settle only after ~20-30 ms of back-to-back HBM streaming
-(profiles/r60_sustain_probe.log), so the read-dominant ceiling probe (>= 150 ms of
-streaming) runs on every rank BEFORE the warmup launches, whatever --warmup is.
+(profiles/r60_sustain_probe.log), so every rank streams for >= 150 ms (the read-dominant
+ceiling kernel) BEFORE the warmup launches, whatever --warmup is.
 
-Usage: python bench.py [--gpus N --steps K --warmup W --workload llama3-70b]
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, the roofline fraction from the timed launches).  --full adds the legs that take
+runs of their own: the read-dominant ceiling figures and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs).
+
+Usage: python bench.py [--gpus N --steps K --warmup W --workload llama3-70b] [--full] [--dump-outputs DIR]
        N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -90,13 +95,20 @@ def parse(argv=None):
     ap.add_argument("--shard", action="store_true", help="(the default; kept for old command lines)")
     ap.add_argument("--replicas", type=int, default=0,
                     help="input copies rotated across steps (0 = enough to exceed the 256 MiB Infinity Cache)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the read-dominant ceiling probes "
+                         "(roofline.read_dominant_ceiling*, frac_of_ceiling*) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write the outputs of the last timed step as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of outputs too large to write whole)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--cpu-sample-seconds", type=float, default=15.0)
     ap.add_argument("--events", default="span", choices=["step", "span"])
     ap.add_argument("--no-copy-ceiling", action="store_true",
-                    help="skip the read-dominant ceiling probe (it also warms the clocks before the warmup)")
+                    help="skip the clock warm-up streaming before the warmup launches and, with --full, the "
+                         "read-dominant ceiling probes it belongs to")
     ap.add_argument("--clock-warm-ms", type=float, default=150.0,
-                    help="ms of ceiling-probe streaming before the warmup launches (clock ramp)")
+                    help="ms of ceiling-kernel streaming before the warmup launches (clock ramp)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the (untimed) gather-to-rank-0 leg")
     ap.add_argument("--write-dir", default=None,
                     help="after the timed region: every rank copies its packed shard to the host and writes it as "
@@ -144,12 +156,12 @@ def make_set(shapes, seed0, dev, dtype=torch.bfloat16, only=None):
     return tensors
 
 
-def stream_ceiling(dev, stream, warm_ms, nbytes=1 << 30, iters=20):
+def stream_ceiling(dev, stream, warm_ms, nbytes=1 << 30, iters=20, measure=True):
     """Read-dominant ceiling: the library's awq_stream_ceiling kernel (the quantizer's memory
     structure — one wave per 4 KiB, 16-B nt loads — and its read:write ratio, 4 : 1 against
     the packed quantizer's 4096 : 1064, without the arithmetic), read + write counted.  Runs
     first, for >= warm_ms of back-to-back streaming, so the timed region starts on settled
-    clocks."""
+    clocks.  measure=False: the clock warm-up alone (a plain run), returns None."""
     from awq_quantizer import _hip
     src = torch.empty(nbytes // 4, dtype=torch.int32, device=dev).fill_(1)
     dst = torch.empty(nbytes // 16, dtype=torch.int32, device=dev)
@@ -160,6 +172,8 @@ def stream_ceiling(dev, stream, warm_ms, nbytes=1 << 30, iters=20):
         torch.cuda.synchronize(dev)
         if (time.perf_counter() - t0) * 1e3 >= warm_ms:
             break
+    if not measure:
+        return None
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record(stream)
     for _ in range(iters):
@@ -169,6 +183,41 @@ def stream_ceiling(dev, stream, warm_ms, nbytes=1 << 30, iters=20):
     gbs = 1.25 * nbytes * iters / (a.elapsed_time(b) / 1e3) / 1e9
     del src, dst
     return gbs
+
+
+DUMP_BYTES = 48 << 20      # all files of one --dump-outputs directory together
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, fields, prefix=""):
+    """--dump-outputs: write the outputs of the last timed step, one file per output field,
+    out_dir/<prefix><field>.npy.  fields: field -> that field's tensors in tensor order; a file
+    is their flattened values end to end, integer outputs as float64 (exact for int32 words),
+    floating-point outputs as float32 (float64 stays float64).  The directory's byte budget is
+    split evenly over the fields and a field's over its tensors: a tensor within its share is
+    written whole, a larger one as its share of elements at sorted indices drawn from a CPU
+    generator seeded per field, so the same arguments give the same positions in every run and
+    every build.  Returns {file: elements}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, (field, tensors) in enumerate(fields.items()):
+        wide = any(not t.dtype.is_floating_point or t.dtype == torch.float64 for t in tensors)
+        np_dtype, tdtype = (np.float64, torch.float64) if wide else (np.float32, torch.float32)
+        quota = max(1, DUMP_BYTES // len(fields) // np.dtype(np_dtype).itemsize // max(1, len(tensors)))
+        g = torch.Generator().manual_seed(DUMP_SEED + k)
+        parts = []
+        for t in tensors:
+            flat = t.detach().reshape(-1)
+            if flat.numel() > quota:
+                idx = torch.randint(flat.numel(), (quota,), generator=g).sort().values
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.to(tdtype).cpu())
+        name = f"{prefix}{field}.npy"
+        arr = torch.cat(parts).numpy() if parts else np.empty(0, np_dtype)
+        np.save(os.path.join(out_dir, name), arr)
+        written[name] = int(arr.size)
+    return written
 
 
 def host_cpus():
@@ -489,7 +538,7 @@ def main():
     # the set is allocated: a 1 GiB buffer runs the structure ~1.5 % faster than a 128 GiB one
     # (profiles/round2/r2g_mix_probe_sizes.log), and the kernel streams 141 GB
     ceiling_fp, fp_bytes = None, 0
-    if not args.no_copy_ceiling and in_bytes >= (4 << 30):
+    if args.full and not args.no_copy_ceiling and in_bytes >= (4 << 30):
         fp_bytes = min(in_bytes // (1 << 30), 128) << 30
         ceiling_fp = stream_ceiling(dev, stream, args.clock_warm_ms, nbytes=fp_bytes, iters=5)
         torch.cuda.empty_cache()
@@ -507,8 +556,8 @@ def main():
     algo_bytes = batches[0].algorithmic_bytes()
 
     barrier = D.barrier
-    # clock warm-up on every rank (and the ceiling figure) before the warmup launches
-    ceiling = None if args.no_copy_ceiling else stream_ceiling(dev, stream, args.clock_warm_ms)
+    # clock warm-up on every rank (and, with --full, the ceiling figure) before the warmup launches
+    ceiling = None if args.no_copy_ceiling else stream_ceiling(dev, stream, args.clock_warm_ms, measure=args.full)
     for i in range(args.warmup):
         batches[i % reps].run(stream)
     torch.cuda.synchronize()
@@ -541,6 +590,11 @@ def main():
     elapsed = D.max_over_ranks(elapsed, dev)
     kern_max_s = D.max_over_ranks(kern_avg_s, dev)
     per_rank = D.all_gather_floats([kern_avg_s * 1e6, float(elems)], dev)   # [kernel us, elements] by rank
+    if args.dump_outputs:
+        last = batches[(args.steps - 1) % reps]          # the batch the last timed step ran
+        dump_outputs(args.dump_outputs, {f: [last.out[n][f] for n in last.names] for f in last.out[last.names[0]]},
+                     prefix=f"rank{rank}." if world > 1 else "")
+        del last
     del batches[1:]
     torch.cuda.empty_cache()
     gather = (gather_leg(batches[0], rank, world, dev, backend, shard_owner=owner,
@@ -626,7 +680,7 @@ def main():
         hv["ceiling_footprint_bytes"] = fp_bytes if ceiling_fp else 1 << 30
         hv["read_dominant_ceiling_1gib"] = round(ceiling, 1)
         hv["frac_of_ceiling_1gib"] = round(achieved / ceiling, 4)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_sample_seconds, args.group_size, dtype,
                                             search=(args.search_grid, args.search_candidates)
                                             if args.mode == "search" else None)
@@ -704,7 +758,7 @@ def main_act(args):
         return [q.quantize_layer_group(ws, x) for ws, x in groups]
 
     if not args.no_copy_ceiling:
-        stream_ceiling(dev, stream, args.clock_warm_ms)           # clock warm-up, as the main bench
+        stream_ceiling(dev, stream, args.clock_warm_ms, measure=False)   # clock warm-up, as the main bench
     for _ in range(max(1, args.warmup)):
         res = step()
     torch.cuda.synchronize()
@@ -717,6 +771,12 @@ def main_act(args):
     D.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
     best = [r["best"] for r in res]
+    if args.dump_outputs:
+        per_linear = [r for grp in res for r in grp["results"].values()]
+        fields = {f: [r[f] for r in per_linear] for f in ("qweight", "qzeros", "scales")}
+        fields.update({f: [grp[f] for grp in res] for f in ("input_scale", "losses")})
+        fields["best"] = [torch.tensor(best)]
+        dump_outputs(args.dump_outputs, fields, prefix=f"rank{rank}." if world > 1 else "")
     # the loss kernel alone: same weights, statistics, table and reciprocal table
     prep = []
     for ws, x in groups:
@@ -762,7 +822,7 @@ def main_act(args):
                        "bits": args.bits, "symmetric": args.symmetric, "duo_scaling": True, "best_ratio": best,
                        "parallelism": f"replica{world} (every rank its own block)"},
             "roofline": roof}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = act_cpu_baseline(min(args.cpu_sample_seconds, 15.0), n_grid, args.act_tokens, dtype,
                                                 args.bits, args.symmetric, gs)
     print(json.dumps(line), flush=True)

@@ -9,7 +9,7 @@
 # shorthands:
 #   pytest[=<pytest args>]   full GPU suite (default) or a selection, 120 s per test
 #   smoke                    __graft_entry__.smoke()
-#   bench[=<bench.py args>]  bench.py line
+#   bench[=<bench.py args>]  bench.py line (bare: --full, with the ceiling figures and the CPU baseline)
 #   rocprof_bench            rocprofv3 --kernel-trace --stats of the default bench (20 launches)
 #   pmc=<regex>=<counter>=<python args>   one rocprofv3 --pmc pass (kernel-trace only)
 # e.g.  gpurun -- 'bash scripts/gpu_run.sh r3a pytest smoke bench rocprof_bench'
@@ -27,7 +27,7 @@ for step in "$@"; do
     pytest=*) name=pytest_$n; secs=900
             cmd="python -u -m pytest -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider ${step#pytest=}" ;;
     smoke) name=smoke; secs=300; cmd="python -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")'" ;;
-    bench) name=bench; secs=600; cmd="python bench.py" ;;
+    bench) name=bench; secs=600; cmd="python bench.py --full" ;;
     bench=*) name=bench_$n; secs=600; cmd="python bench.py ${step#bench=}" ;;
     rocprof_bench) name=rocprof_bench; secs=600
             cmd="rocprofv3 --kernel-trace --stats --kernel-include-regex awq_fast_kernel -d $OUT/trace -o bench --output-format csv -- python bench.py --steps 20 --no-cpu-baseline" ;;

@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 RX='awq_fast_kernel|awq_stream_ceiling_kernel'
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline ${WL_ARGS:-}"
+B="python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline ${WL_ARGS:-}"
 step() { local name=$1; shift; echo "=== $name"; timeout -s KILL 240 rocprofv3 --kernel-include-regex "$RX" --pmc "$@" \
            --output-format csv -d "$OUT/$name" -o run -- $B > "$OUT/$name.log" 2>&1; local rc=$?; echo "rc=$rc";
          [ $rc -eq 0 ] || exit $rc; python scripts/pmc_summary.py "$OUT/$name" > "$OUT/$name.summary.json";

@@ -510,7 +510,7 @@ def test_bench_two_ranks_shard_gpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(root, "bench.py"), "--gpus", "2",
            "--steps", "3", "--warmup", "1", "--workload", "opt-125m", "--replicas", "1",
-           "--no-cpu-baseline", "--clock-warm-ms", "20", "--write-dir", str(tmp_path)]
+           "--full", "--no-cpu-baseline", "--clock-warm-ms", "20", "--write-dir", str(tmp_path)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -556,6 +556,83 @@ def test_bench_cpu_baseline_extrapolates(monkeypatch):
     assert cb["kind"] == "port" and cb["cores"] == 2 and cb["node_cpus"] == os.cpu_count()
     assert cb["value"] > 0 and cb["c1_full"]["seconds"] > 0 and "EXTRAPOLATED" in cb["sample"]
     assert cb["shapes_sampled"] == len(bench.WORKLOADS["opt-125m"])
+
+
+def test_bench_full_and_dump_flags():
+    """--full (the legs beside the headline figure) is off by default; --dump-outputs takes a directory."""
+    import bench
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "d", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "d" and a.steps == 7
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """dump_outputs: int32 words as float64, fp16 as float32; a tensor within its share of the
+    byte budget is written whole, a larger one as a seeded sample at sorted positions, the same
+    in every call."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(3)
+    big = torch.randint(-2 ** 31, 2 ** 31 - 1, (37, 101), generator=g, dtype=torch.int64).to(torch.int32)
+    small = torch.tensor([[-2 ** 31, 2 ** 31 - 1, -1]], dtype=torch.int32)
+    sc = [torch.randn(5, 7, generator=g).to(torch.float16), torch.randn(300, generator=g).to(torch.float16)]
+    fields = {"qweight": [big, small], "scales": sc}
+    # 2 fields: 1600 B each; qweight 200 float64 -> 100 per tensor, scales 400 float32 -> 200 per tensor
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3200)
+    n = bench.dump_outputs(str(tmp_path / "a"), fields)
+    assert n == {"qweight.npy": 103, "scales.npy": 235}
+    qw, s = np.load(tmp_path / "a" / "qweight.npy"), np.load(tmp_path / "a" / "scales.npy")
+    assert qw.dtype == np.float64 and s.dtype == np.float32
+    assert qw.nbytes + s.nbytes <= 3200
+    idx = torch.randint(big.numel(), (100,), generator=torch.Generator().manual_seed(bench.DUMP_SEED)).sort().values
+    assert np.array_equal(qw[:100], big.reshape(-1)[idx].numpy().astype(np.float64))
+    assert qw[100:].tolist() == [-2.0 ** 31, 2.0 ** 31 - 1, -1.0]
+    assert np.array_equal(s[:35], sc[0].reshape(-1).float().numpy())
+    idx = torch.randint(300, (200,), generator=torch.Generator().manual_seed(bench.DUMP_SEED + 1)).sort().values
+    assert np.array_equal(s[35:], sc[1][idx].float().numpy())
+    bench.dump_outputs(str(tmp_path / "b"), fields, prefix="rank1.")
+    assert sorted(os.listdir(tmp_path / "b")) == ["rank1.qweight.npy", "rank1.scales.npy"]
+    assert np.array_equal(np.load(tmp_path / "b" / "rank1.qweight.npy"), qw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("full", [False, True], ids=["plain", "full"])
+def test_bench_plain_and_full_run_gpu(tmp_path, monkeypatch, capsys, full):
+    """One in-process bench run on the c1 workload.  A plain run times exactly --steps steps and
+    prints the headline line with ms_per_step and neither the ceiling probe nor the CPU baseline;
+    --full adds both.  --dump-outputs writes the last timed step's outputs: regenerated from the
+    same seeds, they equal the oracle's bit for bit."""
+    import numpy as np
+    import bench
+    from oracle import awq_oracle as orc
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    out = tmp_path / "dump"
+    argv = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c1", "--replicas", "1",
+            "--clock-warm-ms", "20", "--dump-outputs", str(out)]
+    if full:
+        argv += ["--full", "--cpu-sample-seconds", "0.2"]
+    monkeypatch.setattr(sys, "argv", argv)
+    bench.main()
+    line = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+    assert line["metric"] == bench.METRIC and line["unit"] == "GB/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["steps"] == 2 and line["n_gpus"] == 1
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(1024 * 4096 * 2 / (line["ms_per_step"] / 1e3) / 1e9, rel=1e-2)
+    assert 0 < line["roofline"]["frac"] < 1
+    assert ("cpu_baseline" in line) == full and ("read_dominant_ceiling" in line["roofline"]) == full
+    if full:
+        assert line["cpu_baseline"]["value"] > 0 and line["roofline"]["read_dominant_ceiling"] > 0
+    assert sorted(os.listdir(out)) == ["qweight.npy", "qzeros.npy", "scales.npy"]
+    x = bench.make_set(bench.shapes_of("c1"), 0, torch.device("cuda", 0))["t0000"].cpu()
+    ref = orc.quantize(x, bits=4, group_size=128, symmetric=False)
+    want = {"qweight": orc.pack_rows(ref["tensor_q"], 4, 0), "qzeros": orc.pack_rows(ref["zero_points"], 4, 0),
+            "scales": ref["scales"]}
+    for f, w in want.items():
+        got = np.load(out / f"{f}.npy")
+        assert got.dtype == (np.float32 if f == "scales" else np.float64), f
+        assert np.array_equal(got, w.reshape(-1).to(torch.float64).numpy()), f
 
 
 def test_act_stats_file_and_flags(tmp_path):
