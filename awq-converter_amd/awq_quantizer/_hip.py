@@ -114,6 +114,8 @@ SIGNATURES = {
     "awq_dequantize_packed": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _P, _P]),
     "awq_pack_rows": (_I32, [_P, _I64, _I64, _I32, _I32, _P, _P]),
     "awq_selftest": (_I32, [_I32, _P, _P]),
+    "awq_quant_error_work_bytes": (_I64, [_I64, _I64, _I64]),
+    "awq_quant_error": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "awq_stream_table_bytes": (_I64, [_I64]),
     "awq_stream_start": (_I32, [ctypes.POINTER(StreamItem), _I32, ctypes.POINTER(StreamConfig),
                                 ctypes.POINTER(ctypes.c_void_p)]),
@@ -427,6 +429,29 @@ def pack_rows(v, rows, n, bits, qmin, out) -> None:
     rc = load_library().awq_pack_rows(ptr(v), rows, n, bits, qmin, ptr(out),
                                       ctypes.c_void_p(stream_ptr(out.device)))
     check(rc, "awq_pack_rows")
+
+
+def quant_error(w: torch.Tensor, rows: int, K: int, L: int, bits: int, symmetric: bool, qweight, qzeros, scales,
+                totals: bool = True):
+    """awq_quant_error: what the packed result costs against w (device, contiguous, [rows, K]).
+    -> (group_stats fp32 [4, rows * G]: sum |d|, sum d^2, sum w^2, max |d|; group_nonfinite int32
+    [rows * G]; totals fp64 [5]: the three sums, max |d|, non-finite count — None unless asked),
+    all on w's device.  Allocates the fp64 workspace."""
+    if w.dtype not in AWQ_DTYPE:
+        raise RuntimeError(f"awq_quant_error: unsupported weight dtype {w.dtype}")
+    lib = load_library()
+    nbytes = lib.awq_quant_error_work_bytes(rows, K, L)
+    if nbytes < 0:
+        raise RuntimeError(f"awq_quant_error_work_bytes failed: {last_error()}")
+    G = -(-K // L) if K else 0
+    stats = torch.empty((4, rows * G), dtype=torch.float32, device=w.device)
+    bad = torch.empty(rows * G, dtype=torch.int32, device=w.device)
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=w.device) if totals else None
+    tot = torch.empty(5, dtype=torch.float64, device=w.device) if totals else None
+    check(lib.awq_quant_error(ptr(w), AWQ_DTYPE[w.dtype], rows, K, L, bits, int(bool(symmetric)), ptr(qweight),
+                              ptr(qzeros), ptr(scales), ptr(stats), ptr(bad), ptr(work), ptr(tot), _stream(w)),
+          "awq_quant_error")
+    return stats, bad, tot
 
 
 def selftest(which: int, device: torch.device) -> int:

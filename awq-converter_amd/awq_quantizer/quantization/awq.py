@@ -676,3 +676,108 @@ class AWQQuantizer:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
         _hip.dequantize_packed(packed["qweight"], packed["qzeros"], packed["scales"], rows, K, L, bits, sym, out)
         return out if dtype == torch.float32 else out.to(dtype)
+
+    # ------------------------------------------------------------------ quantization-error report
+    def quantization_error(self, tensor: torch.Tensor, result: Dict[str, torch.Tensor],
+                           per_group: bool = False) -> dict:
+        """What `result` costs against the original `tensor`: the reference's only quality figure
+        (torch.abs(tensor - dequantized).mean(), its test_quantization.py:155-160) and its
+        relatives, from one pass over the weights and the PACKED result (include/awq_hip.h
+        awq_quant_error) — so it measures any scale method and any checkpoint this tool wrote.
+
+        result: a quantize_packed() dict, or a reference-format dict (tensor_q / scales /
+        zero_points; packed on the device with its own bits / symmetric).  Shape, bits and group
+        size are the dict's.  Like dequantize(), 0-d or 1-d scales (small-tensor results) raise
+        IndexError.  Returns plain Python numbers: numel, nonfinite (elements whose error, its
+        square or w^2 is NaN / inf: they enter no sum), sum_abs, sum_sq, sum_w_sq,
+        mean_abs_error = sum_abs / (numel - nonfinite) (NaN when nothing is finite), mse,
+        max_abs_error, snr_db = 10 log10(sum_w_sq / sum_sq) (inf when sum_sq == 0).
+        A result of quantize_layer_group / --act_stats carries "input_scale" and quantizes
+        W * diag(input_scale) (the caller folds 1 / input_scale into the op producing x): the
+        report is then taken against RN(W * input_scale) in the weight dtype (awq_apply_input_scale),
+        i.e. in the scaled domain the checkpoint lives in, and "input_scaled" is True.
+        per_group=True adds the device tensors group_abs / group_sq / group_w_sq / group_max (fp32
+        [rows, G]) and group_nonfinite (int32 [rows, G])."""
+        self._check_input(tensor)
+        if tensor.dtype == torch.float64:
+            raise RuntimeError("quantization_error: float64 weights are not supported")
+        bits = int(result["bits"].item())
+        L = int(result["group_size"].item())
+        sym = bool(result["symmetric"].item())
+        scales = result["scales"]
+        if scales.dim() != 2:
+            raise IndexError(f"too many indices for tensor of dimension {scales.dim()}")
+        n = tensor.numel()
+        rows = 1 if tensor.dim() <= 1 else tensor.shape[0]
+        K = n // max(rows, 1)
+        G = -(-K // L) if K else 0
+        per = 32 // bits
+        if tuple(scales.shape) != (rows, G):
+            raise IndexError(f"scales shape {tuple(scales.shape)} does not match {rows} rows x {G} groups")
+        in_scale = result.get("input_scale")
+        if in_scale is not None and (tensor.dim() != 2 or tuple(in_scale.shape) != (K,)):
+            raise ValueError(f"quantization_error: input_scale {tuple(in_scale.shape)} does not match a 2-D weight "
+                             f"[out, {K}] (tensor shape {tuple(tensor.shape)})")
+        dev = self.compute_device()
+        w = _device_input(tensor, dev)
+        if in_scale is not None:     # the result quantizes W * diag(input_scale): measure against that
+            w = _hip.apply_input_scale(w, in_scale.to(dev, torch.float32).contiguous())
+        scales = scales.to(dev, torch.float16).contiguous()
+        if "qweight" in result:
+            if "shape" in result and tuple(int(v) for v in result["shape"].tolist()) != tuple(tensor.shape):
+                raise ValueError(f"quantization_error: result shape {result['shape'].tolist()} != tensor shape "
+                                 f"{list(tensor.shape)}")
+            qweight = result["qweight"].to(dev, torch.int32).contiguous()
+            qzeros = result["qzeros"].to(dev, torch.int32).contiguous()
+        else:
+            tq, zp = result["tensor_q"], result["zero_points"]
+            if tuple(tq.shape) != tuple(tensor.shape) or tuple(zp.shape) != (rows, G):
+                raise ValueError(f"quantization_error: tensor_q {tuple(tq.shape)} / zero_points {tuple(zp.shape)} "
+                                 f"do not match tensor shape {tuple(tensor.shape)}")
+            qmin = -(1 << (bits - 1)) if sym else 0
+            qweight = torch.empty((rows, -(-K // per)), dtype=torch.int32, device=dev)
+            qzeros = torch.empty((rows, -(-G // per)), dtype=torch.int32, device=dev)
+            if n:
+                _hip.pack_rows(tq.to(dev, torch.int32).contiguous(), rows, K, bits, qmin, qweight)
+                _hip.pack_rows(zp.to(dev, torch.int32).contiguous(), rows, G, bits, qmin, qzeros)
+        if tuple(qweight.shape) != (rows, -(-K // per)) or tuple(qzeros.shape) != (rows, -(-G // per)):
+            raise ValueError(f"quantization_error: qweight {tuple(qweight.shape)} / qzeros {tuple(qzeros.shape)} "
+                             f"do not match tensor shape {tuple(tensor.shape)}")
+        stats, bad, totals = _hip.quant_error(w, rows, K, L, bits, sym, _aligned(qweight), qzeros, scales)
+        out = error_report(n, totals.tolist())
+        out["input_scaled"] = in_scale is not None
+        if per_group:
+            out.update(group_abs=stats[0].view(rows, G), group_sq=stats[1].view(rows, G),
+                       group_w_sq=stats[2].view(rows, G), group_max=stats[3].view(rows, G),
+                       group_nonfinite=bad.view(rows, G))
+        return out
+
+    def quantization_error_model(self, tensors: Dict[str, torch.Tensor],
+                                 results: Dict[str, Dict[str, torch.Tensor]]) -> Dict[str, dict]:
+        """quantization_error for every result; failures (and results without a source tensor)
+        are logged and skipped, like quantize_model."""
+        out = {}
+        for name, res in results.items():
+            try:
+                if name not in tensors:
+                    raise KeyError(f"no source tensor named {name}")
+                out[name] = self.quantization_error(tensors[name], res)
+            except Exception as e:  # skip and continue
+                self.logger.error(f"Error measuring tensor: {name}, error: {e}")
+                continue
+        return out
+
+
+def error_report(numel: int, totals) -> dict:
+    """The report's numbers from awq_quant_error's totals (sum |d|, sum d^2, sum w^2, max |d|,
+    non-finite count) of a tensor — or of a model: the sums and counts add, the max is the max."""
+    sum_abs, sum_sq, sum_w_sq, max_abs, bad = (float(v) for v in totals)
+    finite = int(numel) - int(bad)
+    if sum_sq == 0.0:
+        snr = math.inf
+    else:
+        snr = 10.0 * math.log10(sum_w_sq / sum_sq) if sum_w_sq > 0.0 else -math.inf
+    return {"numel": int(numel), "nonfinite": int(bad), "sum_abs": sum_abs, "sum_sq": sum_sq, "sum_w_sq": sum_w_sq,
+            "mean_abs_error": sum_abs / finite if finite else math.nan,
+            "mse": sum_sq / finite if finite else math.nan,
+            "max_abs_error": max_abs, "snr_db": snr}

@@ -295,6 +295,33 @@ int awq_dequantize_packed(const int32_t* qweight, const int32_t* qzeros, const u
 int awq_pack_rows(const int32_t* v, int64_t rows, int64_t n, int bits, int qmin, int32_t* packed,
                   void* stream);
 
+/* ---- Quantization-error report (additive to ABI 17; no reference counterpart beyond the
+ * per-tensor torch.abs(tensor - dequantized).mean() its test_quantization.py:155-160 prints) ----
+ * What the packed result (qweight / qzeros / scales above, any scale method) costs against the
+ * original weights w [rows, K] (bf16 / fp16 / fp32; fp64 and group_size > 512: AWQ_EUNSUPPORTED),
+ * in one pass over w and qweight, without materialising the dequantized tensor.  Per element k of
+ * group g:  dq = fp32(fp16(fp16(q - z) * s)) (awq_dequantize_packed's arithmetic),
+ *   d = RN_f32(fp32(w) - dq), a = |d|, e = RN_f32(d d), p = RN_f32(fp32(w) fp32(w)), no contraction;
+ *   an element whose d, e or p is NaN / +-inf adds nothing to the sums or the max and counts 1.
+ * Level 1, per group, fp32: the sums of a, e, p over the group's finite elements in
+ *   awq_quantize_search's canonical order (8-element chunks in sequence from +0, then the pairwise
+ *   tree over 64 chunk slots, adjacent pairs first), the max of a (+0 if none), the count (int32).
+ * Level 2, per tensor, fp64: each of the three sums over the flat groups r G + g in
+ *   awq_act_search_select's four ascending levels (64-group sub-blocks, 1024-group blocks,
+ *   32-block super-blocks, the super-blocks); the max of the maxes; the sum of the counts.
+ * Kernels, all with the same bits: group_size 32 / 64 / 128 / 256 with K % group_size == 0 and 16-B
+ * aligned w / qweight: the streaming kernel (one wave per 2048 elements); everything else
+ * (any K, tail groups, element-aligned pointers): one wave per group.  rows * G < 2^31. */
+
+/* bytes of the fp64 workspace awq_quant_error needs (< 0: unsupported shape) */
+int64_t awq_quant_error_work_bytes(int64_t rows, int64_t K, int64_t group_size);
+/* group_stats fp32 [4, rows*G]: sum|d|, sum d^2, sum w^2, max|d| per group; group_nonfinite int32 [rows*G];
+ * totals fp64 [5] (device): the three level-2 sums, max|d|, non-finite count.  group_stats / group_nonfinite
+ * are caller buffers and are always written (they are level 1); totals may be NULL (work is then unused). */
+int awq_quant_error(const void* w, int dtype, int64_t rows, int64_t K, int64_t group_size, int bits, int symmetric,
+                    const int32_t* qweight, const int32_t* qzeros, const uint16_t* scales, float* group_stats,
+                    int32_t* group_nonfinite, double* work, double* totals, void* stream);
+
 /* ---- Host streaming pipeline ----------------------------------
  * Replaces the CLI's read -> quantize -> collect loop (reference main.py:216-392, which
  * loads every file whole and then quantizes tensor by tensor): tensors are pread from their
