@@ -133,6 +133,8 @@ SIGNATURES = {
     "awq_act_scale_table": (_I32, [_P, _P, _I64, _I32, _P, _P]),
     "awq_act_scale_table_ws": (_I32, [_P, _P, _I64, _I32, _P, _P, _P]),
     "awq_quantize_groups_scaled": (_I32, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "awq_quantize_clip_scaled": (_I32, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P,
+                                        _P, _P, _I64, _P]),
     "awq_act_recip_table": (_I32, [_P, _I32, _I64, _P, _P]),
     "awq_act_search_losses": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
     "awq_act_search_select": (_I32, [_P, _I32, _I64, _P, _I64, _P, _P, _P, _P, _P]),
@@ -578,6 +580,28 @@ def quantize_groups_scaled(w: torch.Tensor, s: torch.Tensor, L: int, bits: int, 
     check(load_library().awq_quantize_groups_scaled(ptr(w), AWQ_DTYPE[w.dtype], rows, K, L, bits, int(bool(symmetric)),
                                                     ptr(s), ptr(qweight), ptr(qzeros), ptr(scales), _stream(w)),
           "awq_quantize_groups_scaled")
+
+
+def quantize_clip_scaled(w: torch.Tensor, s: torch.Tensor, x_sq: torch.Tensor, L: int, bits: int, symmetric: bool,
+                         n_grid: int, n_candidates: int, *, rscale: Optional[torch.Tensor] = None, qweight=None,
+                         qzeros=None, scales=None, best_idx=None, group_loss: Optional[torch.Tensor] = None,
+                         loss_offset: int = 0) -> None:
+    """Activation-aware clip search + packed RTN of w * diag(s) with each group's winning range
+    (awq_quantize_clip_scaled).  w [rows, K] device, contiguous; s, x_sq fp32 [K]; rscale:
+    act_recip_table(s[None])[0] or None (IEEE divisions, same bits).  group_loss fp32
+    [2, stride]: this weight's groups are written at columns [loss_offset, loss_offset + rows * G)."""
+    rows, K = w.shape
+    loss_ptr, stride = None, 0
+    if group_loss is not None:
+        stride = group_loss.shape[1]
+        if group_loss.dtype != torch.float32 or group_loss.shape[0] != 2 or not group_loss.is_contiguous() \
+                or loss_offset < 0 or loss_offset + rows * (K // L) > stride:
+            raise ValueError("group_loss must be a contiguous fp32 [2, stride] holding this weight's groups at loss_offset")
+        loss_ptr = ctypes.c_void_p(group_loss.data_ptr() + 4 * loss_offset)
+    check(load_library().awq_quantize_clip_scaled(ptr(w), AWQ_DTYPE[w.dtype], rows, K, L, bits, int(bool(symmetric)),
+                                                  ptr(s), ptr(rscale), ptr(x_sq), n_grid, n_candidates, ptr(qweight),
+                                                  ptr(qzeros), ptr(scales), ptr(best_idx), loss_ptr, stride,
+                                                  _stream(w)), "awq_quantize_clip_scaled")
 
 
 def apply_input_scale(w: torch.Tensor, s: torch.Tensor) -> torch.Tensor:

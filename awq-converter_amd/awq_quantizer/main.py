@@ -77,6 +77,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="scale_method=awq: channel scales x_mean^r instead of x_mean^r / w_mean^(1-r)")
     p.add_argument("--search_max_shrink", type=float, default=0.5,
                    help="scale_method=search: largest shrink of the group range tried")
+    p.add_argument("--act_clip", action="store_true",
+                   help="scale_method=awq with --act_stats: after the channel-scale search, an activation-aware "
+                        "clip search per group (packed output only)")
+    p.add_argument("--clip_grid", type=int, default=20, help="--act_clip: grid size of the range shrinks")
+    p.add_argument("--clip_max_shrink", type=float, default=0.5,
+                   help="--act_clip: largest shrink of the group range tried")
     p.add_argument("--per_channel", action="store_true", help="Use per-channel quantization")
     p.add_argument("--device", type=str, default="cuda" if torch.cuda.is_available() else "cpu",
                    help="Device to use for quantization (cuda, cuda:0, cuda:1, cpu, or 'all' for all GPUs)")
@@ -632,7 +638,8 @@ def quantize_stream(loader, infos: List[TensorInfo], quantizer: AWQQuantizer, de
                     batch_bytes: int = 1 << 30, export_autoawq: bool = False,
                     act_stats: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None,
                     on_done: Optional[Callable[[str, Optional[Dict[str, torch.Tensor]]], None]] = None,
-                    writer: Optional["ChunkWriter"] = None, engine: str = "native") -> None:
+                    writer: Optional["ChunkWriter"] = None, engine: str = "native",
+                    act_clip: Optional[Dict[str, float]] = None) -> None:
     """Quantize `infos` on one GPU.  RTN and the per-group clip search (scale_method
     "search") to the packed or reference format run on the native pipeline
     (quantize_stream_native; `writer`: the ChunkWriter consuming on_done, whose written
@@ -643,7 +650,8 @@ def quantize_stream(loader, infos: List[TensorInfo], quantizer: AWQQuantizer, de
         return quantize_stream_native(loader, infos, quantizer, device, readers, packed, out, lock, logger,
                                       keep_on_device=keep_on_device, on_done=on_done, writer=writer)
     return quantize_stream_python(loader, infos, quantizer, device, readers, lookahead, packed, out, lock, logger,
-                                  memory_efficient, keep_on_device, batch_bytes, export_autoawq, act_stats, on_done)
+                                  memory_efficient, keep_on_device, batch_bytes, export_autoawq, act_stats, on_done,
+                                  act_clip=act_clip)
 
 
 def quantize_stream_python(loader, infos: List[TensorInfo], quantizer: AWQQuantizer, device: str, readers: int,
@@ -651,7 +659,8 @@ def quantize_stream_python(loader, infos: List[TensorInfo], quantizer: AWQQuanti
                            memory_efficient: bool = False, keep_on_device: bool = False,
                            batch_bytes: int = 1 << 30, export_autoawq: bool = False,
                            act_stats: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None,
-                           on_done: Optional[Callable[[str, Optional[Dict[str, torch.Tensor]]], None]] = None) -> None:
+                           on_done: Optional[Callable[[str, Optional[Dict[str, torch.Tensor]]], None]] = None,
+                           act_clip: Optional[Dict[str, float]] = None) -> None:
     """Quantize `infos` on one GPU as a pipeline over batches of tensors (<= batch_bytes of
     input each):
 
@@ -666,8 +675,11 @@ def quantize_stream_python(loader, infos: List[TensorInfo], quantizer: AWQQuanti
 
     act_stats (scale_method="awq"): name -> (x_mean, x_sq); those weights take the
     activation-aware search (AWQQuantizer.quantize_layer_group, one weight per layer group)
-    and carry its "input_scale" in their results."""
+    and carry its "input_scale" in their results.  act_clip ({"clip_grid", "clip_max_shrink"}):
+    those weights also take the activation-aware clip search (quantize_layer_group's clip=True)."""
     t_enter = time.perf_counter()
+    clip_kw = {"clip": True, "clip_grid": int(act_clip["clip_grid"]),
+               "clip_max_shrink": float(act_clip["clip_max_shrink"])} if act_clip else {}
     if not (device.startswith("cuda") and torch.cuda.is_available()):
         quantizer.compute_device()   # raises HipUnavailable: no CPU path
     dev = torch.device(device)
@@ -776,7 +788,7 @@ def quantize_stream_python(loader, infos: List[TensorInfo], quantizer: AWQQuanti
                     try:
                         xm, xs = act_stats[name]
                         searched[name] = quantizer.quantize_layer_group(
-                            {name: dev_in[name]}, x_mean=xm, x_sq=xs, packed=packed)["results"][name]
+                            {name: dev_in[name]}, x_mean=xm, x_sq=xs, packed=packed, **clip_kw)["results"][name]
                     except Exception as e:  # noqa: BLE001  (reference semantics: skip and continue)
                         if logger:
                             logger.error(f"Error quantizing tensor: {name}, error: {e}")
@@ -924,6 +936,18 @@ def main(argv: Optional[List[str]] = None) -> int:
             passthrough = [i for i in index if i.name not in linear]
             ordered = [i for i in ordered if i.name in linear]
             logger.info(f"AutoAWQ export: {len(ordered)} linear weights quantized, {len(passthrough)} copied")
+        act_clip = None
+        if args.act_clip:
+            if args.scale_method != "awq" or not args.act_stats:
+                logger.error("--act_clip needs --scale_method awq and --act_stats")
+                return 1
+            if args.output_format != "packed":
+                logger.error("--act_clip writes packed results only: use --output_format packed")
+                return 1
+            if args.clip_grid < 1 or not 0.0 <= args.clip_max_shrink <= 1.0:
+                logger.error("--act_clip needs --clip_grid >= 1 and --clip_max_shrink in [0, 1]")
+                return 1
+            act_clip = {"clip_grid": args.clip_grid, "clip_max_shrink": args.clip_max_shrink}
         act_stats = None
         if args.act_stats:
             if args.scale_method != "awq":
@@ -940,7 +964,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         from . import distributed as D
         rank, local, world = D.env_world()
         if world > 1:   # torchrun: one process per GPU, LPT shard, RCCL gather to rank 0
-            return _main_distributed(args, loader, ordered, logger, start, passthrough, act_stats)
+            return _main_distributed(args, loader, ordered, logger, start, passthrough, act_stats, act_clip)
         parts = partition_tensors(ordered, len(devices))
         quantizers = {d: AWQQuantizer(bits=args.bits, group_size=args.group_size, symmetric=args.symmetric,
                                       zero_point=args.zero_point, percentile=args.percentile,
@@ -971,7 +995,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                                                                args.memory_efficient, False, 1 << 30, autoawq),
                                   kwargs={"act_stats": act_stats, "on_done": writer.done if writer else None,
                                           "writer": writer if len(devices) == 1 else None,
-                                          "engine": args.stream_engine})
+                                          "engine": args.stream_engine, "act_clip": act_clip})
             th.start()
             threads.append(th)
         for th in threads:
@@ -1043,7 +1067,7 @@ STREAM_OPTS: Dict[str, int] = {}
 
 
 def _main_distributed(args, loader, ordered: List[TensorInfo], logger, start: float,
-                      passthrough: Optional[List[TensorInfo]] = None, act_stats=None) -> int:
+                      passthrough: Optional[List[TensorInfo]] = None, act_stats=None, act_clip=None) -> int:
     """torchrun mode: one process per GPU; rank r quantizes the tensors an LPT partition by
     bytes assigns it (identical on every rank, derived from the header index with no
     exchange; the reference's own partition_tensors, main.py:395-427).  Output
@@ -1103,7 +1127,7 @@ def _main_distributed(args, loader, ordered: List[TensorInfo], logger, start: fl
                         args.output_format in ("packed", "autoawq"), sink, threading.Lock(), logger,
                         args.memory_efficient, keep_on_device=not per_rank, export_autoawq=autoawq,
                         act_stats=act_stats, on_done=writer.done if writer else None, writer=writer,
-                        engine=args.stream_engine)
+                        engine=args.stream_engine, act_clip=act_clip)
     except Exception as e:  # noqa: BLE001  (agreed below: every rank exits 1)
         logger.error(f"rank {rank}: quantization failed: {e}")
         failed = 1

@@ -601,7 +601,8 @@ class AWQQuantizer:
 
     def quantize_layer_group(self, weights: Dict[str, torch.Tensor], activations: Optional[torch.Tensor] = None,
                              *, x_mean: Optional[torch.Tensor] = None, x_sq: Optional[torch.Tensor] = None,
-                             packed: bool = True, table: Optional[torch.Tensor] = None) -> dict:
+                             packed: bool = True, table: Optional[torch.Tensor] = None, clip: bool = False,
+                             clip_grid: int = 20, clip_max_shrink: float = 0.5) -> dict:
         """Activation-aware scale search + quantization of linears that read one input
         (scale_method="awq"; include/awq_hip.h awq_act_*, act_search.py).
 
@@ -611,20 +612,39 @@ class AWQQuantizer:
         W * diag(input_scale) (quantize_packed() result dicts if packed, else quantize()'s,
         device tensors, each with "input_scale"); the caller folds 1 / input_scale into the
         op producing x.  Returns {"results", "input_scale" fp32 [in], "ratio", "best",
-        "losses" fp64 [search_grid] (the candidates' diagonal-MSE losses)}."""
+        "losses" fp64 [search_grid] (the candidates' diagonal-MSE losses)}.
+
+        clip=True adds the activation-aware clip search (awq_quantize_clip_scaled): every group's
+        range is shrunk by (clip_grid - i) / clip_grid, i < min(clip_grid, max(1,
+        int(clip_max_shrink * clip_grid))), and the shrink with the smallest activation-weighted
+        error is kept.  Packed outputs only.  The return value gains "clip": {"loss_before",
+        "loss_after" (the layer group's fp64 loss with candidate 0 / with the winners),
+        "clipped_fraction" (groups whose winner is not candidate 0), "per_weight": name -> the same
+        three for that weight, "best_idx": name -> the winners, int32 [rows * G] on the device}."""
         from .act_search import _check_group, search_layer_group
         if self.scale_method != "awq":
             raise ValueError("quantize_layer_group needs scale_method='awq'")
+        n_clip = 0
+        if clip:
+            if not packed:
+                raise ValueError("clip=True writes packed outputs only (packed=False is not available)")
+            if isinstance(clip_grid, bool) or not isinstance(clip_grid, int) or clip_grid < 1:
+                raise ValueError(f"clip_grid must be a positive integer: {clip_grid}")
+            if not 0.0 <= float(clip_max_shrink) <= 1.0:
+                raise ValueError(f"clip_max_shrink must be in [0, 1]: {clip_max_shrink}")
+            n_clip = min(clip_grid, max(1, int(clip_max_shrink * clip_grid)))
         _check_group(weights, self.group_size)
         self._check_mode()
         dev = self.compute_device()
         # packed outputs of eligible shapes: W * diag(s) quantized in one pass (the scaled copy
         # is never written: awq_quantize_groups_scaled); otherwise the copy, then quantize
-        one_pass = packed and all(
-            _hip.scaled_eligible(w.dtype, w.shape[0], w.shape[1], self.group_size) for w in weights.values())
+        one_pass = packed and (clip or all(
+            _hip.scaled_eligible(w.dtype, w.shape[0], w.shape[1], self.group_size) for w in weights.values()))
         sr = search_layer_group(weights, dev, group_size=self.group_size, bits=self.bits, symmetric=self.symmetric,
                                 n_grid=self.search_grid, duo_scaling=self.duo_scaling, activations=activations,
                                 x_mean=x_mean, x_sq=x_sq, table=table, scale_weights=not one_pass)
+        if clip:
+            return self._clip_layer_group(weights, sr, clip_grid, n_clip)
         results = {}
         for name in weights:
             w = sr["weights"][name]
@@ -641,6 +661,50 @@ class AWQQuantizer:
         self.logger.info(f"awq search over {list(weights)}: ratio {best}/{self.search_grid}")
         return {"results": results, "input_scale": sr["input_scale"], "best": best,
                 "ratio": best / self.search_grid, "losses": sr["losses"], "table": sr["table"]}
+
+    def _clip_layer_group(self, weights, sr: dict, clip_grid: int, n_clip: int) -> dict:
+        """quantize_layer_group's last step with clip=True: every weight through
+        awq_quantize_clip_scaled with the search's input scale, its reciprocals and x_sq; the
+        groups' losses of all weights meet in one [2, total groups] buffer, summed in fp64 by
+        awq_act_search_select (before = candidate 0, after = the winners)."""
+        s, x_sq = sr["input_scale"], sr["x_sq"]
+        K = s.numel()
+        G = K // self.group_size
+        rs = _hip.act_recip_table(s.reshape(1, K)).reshape(K)
+        names = list(weights)
+        counts = [sr["weights"][n].shape[0] * G for n in names]
+        loss = torch.empty((2, sum(counts)), dtype=torch.float32, device=s.device)
+        results, idx, off = {}, {}, 0
+        for name, cnt in zip(names, counts):
+            w = sr["weights"][name]
+            r = self._packed_outputs(w)
+            idx[name] = torch.empty(cnt, dtype=torch.int32, device=s.device)
+            _hip.quantize_clip_scaled(w, s, x_sq, self.group_size, self.bits, self.symmetric, clip_grid, n_clip,
+                                      rscale=rs, qweight=r["qweight"], qzeros=r["qzeros"], scales=r["scales"],
+                                      best_idx=idx[name], group_loss=loss, loss_offset=off)
+            r["input_scale"] = s
+            results[name] = r
+            off += cnt
+        # (the select kernel also copies the winning row of a table: two rows of s keep that in range)
+        two = s.reshape(1, K).expand(2, K).contiguous()
+        total, _, _ = _hip.act_search_select(loss, two)
+        total = total.cpu()
+        per, off, clipped = {}, 0, 0
+        for name, cnt in zip(names, counts):
+            one, _, _ = _hip.act_search_select(loss[:, off:off + cnt].contiguous(), two)
+            one = one.cpu()
+            nz = int((idx[name] != 0).sum().item())
+            per[name] = {"loss_before": float(one[0]), "loss_after": float(one[1]), "clipped_fraction": nz / cnt}
+            self.logger.info(f"awq clip {name}: clipped {nz / cnt:.1%} of {cnt} groups, loss "
+                             f"{float(one[0]):.6g} -> {float(one[1]):.6g}")
+            clipped += nz
+            off += cnt
+        best = int(sr["best"].item())
+        self.logger.info(f"awq search over {names}: ratio {best}/{self.search_grid}, clip {n_clip}/{clip_grid}")
+        return {"results": results, "input_scale": s, "best": best, "ratio": best / self.search_grid,
+                "losses": sr["losses"], "table": sr["table"],
+                "clip": {"loss_before": float(total[0]), "loss_after": float(total[1]),
+                         "clipped_fraction": clipped / sum(counts), "per_weight": per, "best_idx": idx}}
 
     def export_autoawq(self, packed: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """A quantize_packed() result of a 2-D [out_features, in_features] weight in the

@@ -555,7 +555,10 @@ int awq_act_scale_table_ws(const float* x_mean, const float* w_mean, int64_t K, 
  * awq_selftest 1); a quotient through an out-of-range entry is NaN, and a wave whose candidate
  * loss comes out NaN redoes that candidate with IEEE divisions (the same bits in range). */
 int awq_act_recip_table(const float* table, int n_grid, int64_t K, float* rtable, void* stream);
-/* rtable: awq_act_recip_table's output for the same table, or NULL (IEEE divisions) */
+/* rtable: awq_act_recip_table's output for the same table, or NULL (IEEE divisions).
+ * Precondition: every table entry is positive and finite, as awq_act_scale_table produces
+ * (it maps inf / NaN to 1).  The kernel relies on it — RN(w * s) is NaN exactly when w is, so
+ * the weights' NaN flag is taken once per group — and does not check a caller's own table. */
 int awq_act_search_losses(const void* w, int dtype, int64_t rows, int64_t K, int64_t group_size, int bits,
                           int symmetric, const float* table, const float* rtable, int n_grid, const float* x_sq,
                           float* part, int64_t part_stride, void* stream);
@@ -565,6 +568,44 @@ int awq_act_search_select(const float* part, int n_grid, int64_t part_stride, co
 /* out [rows, K] (dtype D) = RN_D(w * s[k]) */
 int awq_apply_input_scale(const void* w, int dtype, int64_t rows, int64_t K, const float* s, void* out,
                           void* stream);
+
+/* ---- Activation-aware clip search (additive to ABI 17): the second step of AutoAWQ's published
+ * method, with the scale search's diagonal loss.  Not in the reference (see above).  For one
+ * weight W [rows, K] of dtype D (bf16 / fp16 / fp32), a column scale s = col_scale fp32 [K]
+ * (positive and finite, as awq_act_scale_table produces; not checked), the statistics x_sq fp32
+ * [K], and 1 <= n_candidates <= n_grid; every step reuses arithmetic pinned above:
+ *   w' = RN_D(w * s[k])                                   (awq_apply_input_scale)
+ *   [mn, mx] of each group of w' as RTN takes it (awq.py:192-199: after the symmetric
+ *       abs-max; a NaN in the group makes both NaN)
+ *   candidate i = 0 .. n_candidates-1: alpha_i = RN_f32((n_grid - i) / n_grid), the range
+ *       RN_D(RN_f32(mn * alpha_i)), RN_D(RN_f32(mx * alpha_i))      (awq_quantize_search)
+ *   scale / zero point of the shrunk range exactly as RTN      (awq.py:202-211)
+ *   per element: q (awq.py:245-248) of w'; dq = fp16(fp16(q - z) * fp16(scale));
+ *       d = RN_f32(dq / s[k]) - w (against the ORIGINAL w); c = x_sq[k] * (d * d), every op
+ *       rounded to fp32, no contraction                      (awq_act_search_losses)
+ *   group loss: each 8-element chunk summed in order from +0, then the pairwise tree over the
+ *       chunks, adjacent pairs first                         (awq_quantize_search's order)
+ *   winner: the first strict minimum; a NaN loss never wins; NaN / inf groups and ties keep
+ *       i = 0.  qweight / qzeros / scales = RTN of w' with the winner's range.
+ * Hence: n_candidates = 1 gives awq_quantize_groups_scaled's bits; s = 1 and x_sq = 1 give
+ * awq_quantize_search's; every group's candidate-0 loss is awq_act_search_losses' partial for
+ * the one-row table [1, K] = s.
+ * col_rscale: awq_act_recip_table(col_scale, 1, K) (entries NaN outside [2^-60, 2^60]), or NULL;
+ *   NULL, or a loss that comes out NaN, means the IEEE division — the same bits either way.
+ * best_idx int32 [rows * G] (the winners) and group_loss fp32 [2, loss_stride] (row 0: candidate
+ *   0's loss of every group, row 1: the winner's; this weight's groups at [0, rows * G), so the
+ *   linears of a layer group write one buffer at their own offsets, and
+ *   awq_act_search_select(group_loss, 2, loss_stride, ...) returns the layer group's fp64 loss
+ *   before and after clipping) may be NULL; at least one output must be given.
+ * Kernels, the same bits: group_size 32 / 64 / 128 / 256 with 16-B aligned w, col_scale,
+ * col_rscale and x_sq: the streaming kernel (one wave per 2048 elements; when G % (32 / bits)
+ * != 0 it first zeroes qzeros on the stream); any other power-of-two group_size in [8, 512]
+ * dividing K, or element-aligned pointers: one wave per group.  Anything else (fp64, larger or
+ * other group sizes, K % group_size != 0): AWQ_EUNSUPPORTED.  Packed outputs only. */
+int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, int64_t K, int32_t group_size, int bits,
+                             int symmetric, const float* col_scale, const float* col_rscale, const float* x_sq,
+                             int n_grid, int n_candidates, int32_t* qweight, int32_t* qzeros, uint16_t* scales,
+                             int32_t* best_idx, float* group_loss, int64_t loss_stride, void* stream);
 
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
