@@ -139,6 +139,7 @@ SIGNATURES = {
     "awq_act_search_losses": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
     "awq_act_search_select": (_I32, [_P, _I32, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "awq_apply_input_scale": (_I32, [_P, _I32, _I64, _I64, _P, _P, _P]),
+    "awq_fold_rows": (_I32, [_P, _I32, _I64, _I64, _P, _P, _P]),
 }
 
 _lib = None
@@ -608,4 +609,27 @@ def apply_input_scale(w: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(w)
     check(load_library().awq_apply_input_scale(ptr(w), AWQ_DTYPE[w.dtype], w.shape[0], w.shape[1], ptr(s), ptr(out),
                                                _stream(w)), "awq_apply_input_scale")
+    return out
+
+
+def fold_rows(w: torch.Tensor, row_scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r, ...] = RN_D(RN_f32(fp32(w[r, ...]) / row_scale[r])) (awq_fold_rows): 1 / s folded into the
+    rows of w — a [rows, K] matrix, or a vector (norm weight, bias: rows = n, K = 1).  w bf16 / fp16 /
+    fp32 on the device, contiguous; row_scale fp32 [rows].  Returns a new tensor unless `out` is given
+    (out may be w itself: in place)."""
+    if w.dim() < 1 or not w.is_contiguous():
+        raise ValueError("fold_rows takes a contiguous tensor of at least one dimension")
+    if w.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise ValueError(f"fold_rows takes bf16 / fp16 / fp32 tensors, got {w.dtype}")
+    rows = w.shape[0]
+    K = w.numel() // rows if rows else 0
+    if row_scale.dtype != torch.float32 or row_scale.numel() != rows or row_scale.device != w.device:
+        raise ValueError(f"row_scale must be fp32 [{rows}] on {w.device}")
+    row_scale = row_scale.contiguous()
+    if out is None:
+        out = torch.empty_like(w)
+    elif out.shape != w.shape or out.dtype != w.dtype or out.device != w.device or not out.is_contiguous():
+        raise ValueError("out must match w (shape, dtype, device, contiguous)")
+    check(load_library().awq_fold_rows(ptr(w), AWQ_DTYPE[w.dtype], rows, K, ptr(row_scale), ptr(out), _stream(w)),
+          "awq_fold_rows")
     return out

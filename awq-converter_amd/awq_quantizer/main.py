@@ -52,6 +52,7 @@ from . import ptfile
 from .stream import device_name, start_warmup
 from .model_loading import TensorInfo, load_model_from_hub
 from .quantization.awq import AWQQuantizer
+from .quantization.linear_weights import CONV1D_MODEL_TYPES, is_linear_weight  # noqa: F401
 from .utils.logger import get_logger
 
 
@@ -80,6 +81,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--act_clip", action="store_true",
                    help="scale_method=awq with --act_stats: after the channel-scale search, an activation-aware "
                         "clip search per group (packed output only)")
+    p.add_argument("--fold_scales", action="store_true",
+                   help="scale_method=awq with --act_stats and --output_format autoawq: search one input scale per "
+                        "layer group of every decoder block (q/k/v, o, gate/up, down), fold 1/s into the op producing "
+                        "that input (norm weight, v_proj / up_proj rows) and write a loadable activation-aware "
+                        "AutoAWQ checkpoint plus awq_scales.safetensors (llama / mistral / qwen2 tensor names)")
     p.add_argument("--clip_grid", type=int, default=20, help="--act_clip: grid size of the range shrinks")
     p.add_argument("--clip_max_shrink", type=float, default=0.5,
                    help="--act_clip: largest shrink of the group range tried")
@@ -464,28 +470,6 @@ def _to_cpu(d: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in d.items()}
 
 
-_NOT_LINEAR = ("embed", "lm_head", "norm", "wte", "wpe", "ln_", "router")
-# model types whose projection weights are transformers Conv1D modules, stored [in, out]
-# (quantizing them as [out, in] would group along the wrong axis): copied, not quantized
-CONV1D_MODEL_TYPES = ("gpt2", "openai-gpt", "imagegpt", "decision_transformer")
-
-
-def is_linear_weight(info: TensorInfo, group_size: int, model_type: Optional[str] = None) -> bool:
-    """The tensors an AutoAWQ checkpoint quantizes: 2-D `*.weight` of nn.Linear layers whose
-    shape the GEMM layout can hold.  Heuristic on names (no module graph in a checkpoint):
-    not embeddings, the LM head, norms, MoE routers (`*.router.*`, and `*.gate.weight` —
-    Mixtral's block_sparse_moe.gate / Qwen-MoE's mlp.gate; `gate_proj` is a linear) which
-    AutoAWQ keeps in fp16, nor any weight of a Conv1D model (CONV1D_MODEL_TYPES)."""
-    if len(info.shape) != 2 or not info.name.endswith(".weight") or not info.dtype.is_floating_point:
-        return False
-    if model_type in CONV1D_MODEL_TYPES:
-        return False
-    if any(s in info.name for s in _NOT_LINEAR) or info.name.endswith(".gate.weight"):
-        return False
-    n, k = info.shape
-    return n % 8 == 0 and k % group_size == 0
-
-
 def model_type_of(loader) -> Optional[str]:
     """config.json's model_type next to the weights, if any."""
     path = os.path.join(getattr(loader, "model_path", "") or "", "config.json")
@@ -497,18 +481,23 @@ def model_type_of(loader) -> Optional[str]:
 
 
 def autoawq_tensors(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthrough: List[TensorInfo],
-                    failed: List[TensorInfo] = ()) -> Dict[str, torch.Tensor]:
+                    failed: List[TensorInfo] = (),
+                    overrides: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """The tensors of an AutoAWQ checkpoint (or one shard of it): `<layer>.qweight/.qzeros/
     .scales` per quantized linear weight; every passthrough tensor and every linear weight
     that failed to quantize copied unchanged (those layers stay unquantized:
-    modules_to_not_convert)."""
+    modules_to_not_convert).  overrides (--fold_scales): name -> tensor written in place of
+    the source's (norm weights and biases with 1 / s folded in)."""
     tensors = {}
     for name, r in quantized.items():
         prefix = name[: -len(".weight")]
         for f in ("qweight", "qzeros", "scales"):
             tensors[f"{prefix}.{f}"] = r[f].contiguous()
     for info in list(passthrough) + list(failed):
-        tensors[info.name] = loader.read(info).contiguous()
+        if overrides and info.name in overrides:
+            tensors[info.name] = overrides[info.name].contiguous()
+        else:
+            tensors[info.name] = loader.read(info).contiguous()
     return tensors
 
 
@@ -537,13 +526,14 @@ def write_autoawq_configs(output_dir: str, args, loader, not_converted: List[str
 
 
 def save_autoawq(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthrough: List[TensorInfo],
-                 output_dir: str, args, logger=None, failed: List[TensorInfo] = ()) -> None:
+                 output_dir: str, args, logger=None, failed: List[TensorInfo] = (),
+                 overrides: Optional[Dict[str, torch.Tensor]] = None) -> None:
     """model.safetensors with `<layer>.qweight/.qzeros/.scales` for every quantized linear
     weight and every other tensor copied unchanged (linear weights that failed to quantize
     included, listed in modules_to_not_convert so the checkpoint still loads), plus the
     configs of write_autoawq_configs."""
     from safetensors.torch import save_file
-    tensors = autoawq_tensors(quantized, loader, passthrough, failed)
+    tensors = autoawq_tensors(quantized, loader, passthrough, failed, overrides)
     save_file(tensors, os.path.join(output_dir, "model.safetensors"), metadata={"format": "pt"})
     write_autoawq_configs(output_dir, args, loader, [i.name[: -len(".weight")] for i in failed], logger)
     if logger:
@@ -875,6 +865,15 @@ def _device_worker(*args, **kwargs) -> None:
             logger.error(f"Quantization on {device} failed: {e}")
 
 
+def _new_quantizer(args, device: str) -> AWQQuantizer:
+    return AWQQuantizer(bits=args.bits, group_size=args.group_size, symmetric=args.symmetric,
+                        zero_point=args.zero_point, percentile=args.percentile, scale_method=args.scale_method,
+                        per_channel=args.per_channel, device=device, search_grid=args.search_grid,
+                        search_max_shrink=args.search_max_shrink, duo_scaling=not args.no_duo_scaling,
+                        logger_name=f"awq_quantizer_{device}", logger_level=args.log_level,
+                        logger_to_file=args.log_file is not None, logger_file_path=args.log_file)
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     logger = None
     t_main = time.time()
@@ -883,6 +882,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         logger = get_logger(name="awq_quantizer", level=args.log_level, to_file=args.log_file is not None,
                             file_path=args.log_file)
         os.makedirs(args.output_dir, exist_ok=True)
+        if args.fold_scales and (args.scale_method != "awq" or not args.act_stats
+                                 or args.output_format != "autoawq"):
+            logger.error("--fold_scales needs --scale_method awq, --act_stats and --output_format autoawq")
+            return 1
 
         if args.multi_gpu or args.device.lower() == "all":
             devices = get_available_gpus(logger)
@@ -936,12 +939,25 @@ def main(argv: Optional[List[str]] = None) -> int:
             passthrough = [i for i in index if i.name not in linear]
             ordered = [i for i in ordered if i.name in linear]
             logger.info(f"AutoAWQ export: {len(ordered)} linear weights quantized, {len(passthrough)} copied")
+        if args.fold_scales:
+            from .quantization.block_plan import SUPPORTED
+            if mtype not in SUPPORTED:
+                logger.error(f"--fold_scales knows the block layout of model types {', '.join(SUPPORTED)}; "
+                             f"config.json says {mtype!r}")
+                return 1
+            if D.env_world()[2] > 1:
+                logger.error("--fold_scales runs in one process (sharding by block under torchrun is not implemented)")
+                return 1
+            if len(devices) > 1:
+                logger.error(f"--fold_scales runs on one GPU, not on {len(devices)} (--multi_gpu / --device all): "
+                             f"name one with --device")
+                return 1
         act_clip = None
         if args.act_clip:
             if args.scale_method != "awq" or not args.act_stats:
                 logger.error("--act_clip needs --scale_method awq and --act_stats")
                 return 1
-            if args.output_format != "packed":
+            if args.output_format != "packed" and not args.fold_scales:
                 logger.error("--act_clip writes packed results only: use --output_format packed")
                 return 1
             if args.clip_grid < 1 or not 0.0 <= args.clip_max_shrink <= 1.0:
@@ -953,26 +969,23 @@ def main(argv: Optional[List[str]] = None) -> int:
             if args.scale_method != "awq":
                 logger.error("--act_stats needs --scale_method awq")
                 return 1
-            if autoawq:
+            if autoawq and not args.fold_scales:
                 logger.error("--act_stats with --output_format autoawq: the searched input scales must be folded "
                              "into the ops producing each input first; use --output_format packed or reference "
-                             "(results carry 'input_scale')")
+                             "(results carry 'input_scale'), or add --fold_scales")
                 return 1
             act_stats = load_act_stats(args.act_stats, logger)
         elif args.scale_method == "awq":
             logger.warning("--scale_method awq without --act_stats: every weight is quantized RTN")
+        if args.fold_scales:
+            return _main_fold_scales(args, loader, index, ordered, passthrough, act_stats, act_clip, devices[0],
+                                     logger, start)
         from . import distributed as D
         rank, local, world = D.env_world()
         if world > 1:   # torchrun: one process per GPU, LPT shard, RCCL gather to rank 0
             return _main_distributed(args, loader, ordered, logger, start, passthrough, act_stats, act_clip)
         parts = partition_tensors(ordered, len(devices))
-        quantizers = {d: AWQQuantizer(bits=args.bits, group_size=args.group_size, symmetric=args.symmetric,
-                                      zero_point=args.zero_point, percentile=args.percentile,
-                                      scale_method=args.scale_method, per_channel=args.per_channel, device=d,
-                                      search_grid=args.search_grid, search_max_shrink=args.search_max_shrink,
-                                      duo_scaling=not args.no_duo_scaling, logger_name=f"awq_quantizer_{d}", logger_level=args.log_level,
-                                      logger_to_file=args.log_file is not None, logger_file_path=args.log_file)
-                      for d in devices}
+        quantizers = {d: _new_quantizer(args, d) for d in devices}
         results: Dict[str, Dict[str, torch.Tensor]] = {}
         lock = threading.Lock()
         lookahead = max(1, args.prefetch_factor * args.batch_size)
@@ -1043,6 +1056,88 @@ def main(argv: Optional[List[str]] = None) -> int:
         else:
             logger.error(f"Error during quantization: {e}")
         return 1
+
+
+def _main_fold_scales(args, loader, index: List[TensorInfo], ordered: List[TensorInfo],
+                      passthrough: List[TensorInfo], act_stats, act_clip, device: str, logger, start: float) -> int:
+    """--fold_scales: the decoder blocks one by one (quantization/block_plan.py) — a block's members
+    and producers read together (the next block read ahead on the reader pool), then
+    AWQQuantizer.quantize_block, export_autoawq per result and D2H; linears in no group take the
+    regular path (RTN).  A block that fails is copied unquantized (modules_to_not_convert) with its
+    norms and biases left unfolded.  Writes model.safetensors (folded norm weights and biases in
+    place of the source's), the configs, and awq_scales.safetensors: every block's "scales"."""
+    from safetensors.torch import save_file
+    from .quantization.block_plan import plan_blocks
+    by_name = {i.name: i for i in index}
+    plan = plan_blocks({i.name: i.shape for i in index}, model_type_of(loader), args.group_size)
+    linear = {i.name for i in ordered}
+    quantizer = _new_quantizer(args, device)
+    try:
+        quantizer.compute_device()
+    except Exception as e:  # noqa: BLE001
+        logger.error(f"Quantization on {device} failed: {e}")
+        return 1
+    clip_kw = {"clip": True, **act_clip} if act_clip else {}
+    results: Dict[str, Dict[str, torch.Tensor]] = {}
+    overrides: Dict[str, torch.Tensor] = {}
+    sidecar: Dict[str, torch.Tensor] = {}
+    blocks = [b for b in plan if all(m in linear for m in b.members())]
+    grouped = {m for b in blocks for m in b.members()}
+    rest = [i for i in ordered if i.name not in grouped]
+    logger.info(f"Scale folding: {len(blocks)} decoder blocks, {len(grouped)} linears in layer groups, "
+                f"{len(rest)} in none (RTN)")
+    inside = [i.name for i in rest if any(i.name.startswith(b.prefix + ".") for b in plan)]
+    if inside:   # none in llama / mistral / qwen2; one reading a folded norm's output would see x / s unscaled
+        logger.warning(f"linears inside a decoder block that belong to no layer group are quantized without an "
+                       f"input scale; if one reads a folded norm's output the checkpoint is wrong: {inside}")
+    with ThreadPoolExecutor(max_workers=max(1, args.num_workers)) as pool:
+        futs = {}
+
+        def submit(k):
+            if k < len(blocks) and k not in futs:
+                futs[k] = {n: pool.submit(loader.read, by_name[n]) for n in blocks[k].tensor_names()}
+
+        submit(0)
+        for k, block in enumerate(blocks):
+            submit(k + 1)
+            try:
+                tensors = {n: f.result() for n, f in futs.pop(k).items()}
+                out = quantizer.quantize_block(tensors, act_stats, block, **clip_kw)
+                exported = {n: _to_cpu(quantizer.export_autoawq(r)) for n, r in out["results"].items()}
+                host_folded = _to_cpu(out["folded"])
+                host_scales = _to_cpu(out["scales"])
+            except Exception as e:  # noqa: BLE001  (the block's linears are copied unquantized)
+                logger.error(f"Error quantizing block {block.prefix}: {e}")
+                continue
+            results.update(exported)
+            overrides.update(host_folded)
+            sidecar.update(host_scales)
+            logger.info(f"Successfully quantized block: {block.prefix} on {device} (folded groups: "
+                        f"{[n for n, g in out['groups'].items() if g['folded']]})")
+    if rest:
+        quantize_stream_python(loader, rest, quantizer, device, readers=args.num_workers,
+                               lookahead=max(1, args.prefetch_factor * args.batch_size), packed=True, out=results,
+                               lock=threading.Lock(), logger=logger, memory_efficient=args.memory_efficient,
+                               keep_on_device=False, export_autoawq=True, act_stats=None)
+    TIMINGS["quantize_s"] = time.time() - start
+    quantized = {i.name: results[i.name] for i in ordered if i.name in results}
+    if not quantized:
+        logger.error("No tensors were successfully quantized")
+        return 1
+    logger.info(f"Successfully quantized {len(quantized)} tensors")
+    logger.info(f"Saving quantized model to {args.output_dir}")
+    try:
+        save_autoawq(quantized, loader, passthrough, args.output_dir, args, logger,
+                     failed=[i for i in ordered if i.name not in quantized], overrides=overrides)
+        save_file({k: v.contiguous() for k, v in sidecar.items()},
+                  os.path.join(args.output_dir, "awq_scales.safetensors"), metadata={"format": "pt"})
+    except Exception as e:  # noqa: BLE001
+        logger.error(f"Failed to save quantized model: {e}")
+        return 1
+    TIMINGS["total_s"] = time.time() - start
+    logger.info(f"Quantization complete in {time.time() - start:.2f} seconds")
+    logger.info("metrics " + json.dumps(run_metrics(ordered, quantized, TIMINGS)))
+    return 0
 
 
 def run_metrics(ordered, quantized, timings) -> Dict[str, float]:

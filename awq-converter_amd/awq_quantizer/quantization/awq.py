@@ -15,7 +15,9 @@ packed int4/int8 words (qweight/qzeros) and fp16 scales on the device for throug
 scale_method="search" (new value, opt-in) runs the per-group clip search of
 include/awq_hip.h awq_quantize_search instead of plain RTN ("mse"/"minmax" stay RTN);
 scale_method="awq" (new value, opt-in) adds quantize_layer_group, the activation-aware
-per-input-channel scale search of include/awq_hip.h awq_act_* (act_search.py).
+per-input-channel scale search of include/awq_hip.h awq_act_* (act_search.py), and
+quantize_block, which runs it over the layer groups of a decoder block (block_plan.py) and
+folds 1 / s into the ops producing each input (awq_fold_rows).
 """
 
 import math
@@ -705,6 +707,107 @@ class AWQQuantizer:
                 "losses": sr["losses"], "table": sr["table"],
                 "clip": {"loss_before": float(total[0]), "loss_after": float(total[1]),
                          "clipped_fraction": clipped / sum(counts), "per_weight": per, "best_idx": idx}}
+
+    def quantize_block(self, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
+                       block, *, clip: bool = False, clip_grid: int = 20, clip_max_shrink: float = 0.5) -> dict:
+        """Activation-aware quantization of one decoder block with the searched input scales
+        folded into the ops that produce each input (block_plan.Block; scale_method="awq").
+
+        tensors: name -> tensor of the block's members and producers (block.tensor_names());
+        stats: name -> (x_mean, x_sq) as load_act_stats returns.  A group's statistics are those
+        of its first member, in table order, that has any; other members' statistics that differ
+        are reported with a warning and ignored.
+
+        Order (fixed):
+          1. attn_out and mlp_out: one quantize_layer_group call on the single member each
+             (clip=True applies to that call), yielding s_out;
+          2. each s_out folded into its producer's rows (v_proj / up_proj, a device copy) and
+             bias with awq_fold_rows;
+          3. attn_in on {q, k, v_folded} and mlp_in on {gate, up_folded}: one joint
+             quantize_layer_group call each, yielding s_in;
+          4. each s_in folded into its norm weight with awq_fold_rows (K = 1).
+        So the v_proj / up_proj that is searched and quantized is the one the checkpoint holds.
+        (AutoAWQ folds the rows after the attn_in search; parity with AutoAWQ is unpinned.)
+
+        A group that is not folded (not foldable — e.g. attn_out with grouped-query shapes — or
+        without statistics) keeps s = 1: its members take quantize_packed, or with clip=True and
+        statistics quantize_layer_group(table=ones [search_grid, in], clip=True), so the clip
+        search still weighs by x_sq.
+
+        Returns device tensors: {"results": name -> quantize_packed()-style dict (no
+        "input_scale": the fold is done), "folded": name -> folded norm weight / bias,
+        "scales": {"<weight>.input_scale": s fp32 [in] for every member, "<weight>.row_scale":
+        fp32 [out] for every row-folded producer}, "groups": group -> {"ratio", "losses",
+        "folded", "clip"}}."""
+        if self.scale_method != "awq":
+            raise ValueError("quantize_block needs scale_method='awq'")
+        self._check_mode()
+        dev = self.compute_device()
+        clip_kw = {"clip": True, "clip_grid": clip_grid, "clip_max_shrink": clip_max_shrink} if clip else {}
+        results, folded, scales, report = {}, {}, {}, {}
+        current: Dict[str, torch.Tensor] = {}     # device tensors, row-folded producers replaced
+
+        def dev_t(name: str) -> torch.Tensor:
+            if name not in current:
+                if name not in tensors:
+                    raise KeyError(f"quantize_block: tensor {name} is missing")
+                current[name] = tensors[name].detach().to(dev).contiguous()
+            return current[name]
+
+        def group_stats(g):
+            have = [m for m in g.members if m in stats]
+            if not have:
+                return None
+            first = stats[have[0]]
+            for m in have[1:]:
+                if not (torch.equal(stats[m][0], first[0]) and torch.equal(stats[m][1], first[1])):
+                    self.logger.warning(f"{m}: activation statistics differ from {have[0]}'s (same input): "
+                                        f"using {have[0]}'s for the {g.name} group")
+            return first
+
+        def run(g) -> Optional[torch.Tensor]:
+            weights = {m: dev_t(m) for m in g.members}
+            st = group_stats(g)
+            K = next(iter(weights.values())).shape[1]
+            fold = g.foldable and st is not None
+            if fold or (clip and st is not None):
+                table = None if fold else torch.ones((self.search_grid, K), dtype=torch.float32, device=dev)
+                out = self.quantize_layer_group(weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw)
+                for m, r in out["results"].items():
+                    results[m] = {k: v for k, v in r.items() if k != "input_scale"}
+                s = out["input_scale"]
+                report[g.name] = {"ratio": out["ratio"] if fold else None, "losses": out["losses"] if fold else None,
+                                  "folded": fold, "clip": out.get("clip")}
+            else:
+                for m, w in weights.items():
+                    results[m] = self.quantize_packed(w)
+                s = torch.ones(K, dtype=torch.float32, device=dev)
+                report[g.name] = {"ratio": None, "losses": None, "folded": False, "clip": None}
+            for m in g.members:
+                scales[f"{m}.input_scale"] = s
+            return s if fold else None
+
+        groups = block.groups
+        for gname in ("attn_out", "mlp_out"):
+            g = groups.get(gname)
+            if g is None:
+                continue
+            s_out = run(g)
+            if s_out is None:
+                continue
+            pw = g.producers[0]
+            current[pw] = _hip.fold_rows(dev_t(pw), s_out)            # a new device tensor: the source stays
+            scales[f"{pw}.row_scale"] = s_out
+            for pb in g.producers[1:]:
+                folded[pb] = _hip.fold_rows(dev_t(pb), s_out)
+        for gname in ("attn_in", "mlp_in"):
+            g = groups.get(gname)
+            if g is None:
+                continue
+            s_in = run(g)
+            if s_in is not None:
+                folded[g.producers[0]] = _hip.fold_rows(dev_t(g.producers[0]), s_in)
+        return {"results": results, "folded": folded, "scales": scales, "groups": report}
 
     def export_autoawq(self, packed: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """A quantize_packed() result of a 2-D [out_features, in_features] weight in the

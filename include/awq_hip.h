@@ -607,6 +607,27 @@ int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, int64_t K, 
                              int n_grid, int n_candidates, int32_t* qweight, int32_t* qzeros, uint16_t* scales,
                              int32_t* best_idx, float* group_loss, int64_t loss_stride, void* stream);
 
+/* ---- Scale folding (additive to ABI 17).  A searched weight is W * diag(s): it is usable only
+ * once 1 / s is folded into whatever produces its input — the preceding norm's weight, or the
+ * rows (and bias) of the preceding linear.  This is that fold, for rows:
+ *   out[r, k] = RN_D( RN_f32( fp32(w[r, k]) / row_scale[r] ) )
+ * w, out [rows, K] of dtype D (bf16 / fp16 / fp32; anything else: AWQ_EUNSUPPORTED); row_scale
+ * fp32 [rows].  The division is the IEEE fp32 division (correctly rounded), its quotient rounded
+ * once, to nearest-even, into D — torch's CPU result of (w.float() / s[:, None]).to(D).
+ * row_scale is not checked (positive and finite when it comes from awq_act_scale_table);
+ * non-finite values propagate as IEEE defines, NaN payloads are unspecified.
+ * out == w is allowed (in place); any other overlap is the caller's error.  Checked in this
+ * order, nothing launched on a failure: negative rows or K: AWQ_EINVAL; the dtype; rows == 0 or
+ * K == 0: AWQ_OK without a launch (the pointers are not looked at: an empty tensor's may be
+ * null); rows * K > 2^60: AWQ_EINVAL; a null pointer: AWQ_EINVAL.
+ * A 1-D vector (a norm weight, a bias) is rows = n, K = 1.
+ * Kernels, the same bits: w and out 16-B aligned and K % 8 == 0: the streaming structure (one
+ * wave per 2048 consecutive elements, 16-B loads and stores, every 8-element chunk inside one
+ * row, the row taken from the element offset); anything else (any K, K = 1, element-aligned
+ * pointers): one element per lane.  Offsets are 64-bit throughout. */
+int awq_fold_rows(const void* w, int dtype, int64_t rows, int64_t K, const float* row_scale, void* out,
+                  void* stream);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
