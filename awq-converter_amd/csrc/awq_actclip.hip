@@ -19,59 +19,27 @@
 // Both go through clip_group below: the per-op arithmetic is the streaming quantizer's
 // (awq_quant.h: group_range, params_from_range, F::quot, quant8_fast / quant8_special), the
 // candidate rule is awq_fast.hip search_range's, the loss chain is awq_actsearch.hip's.
-#include <cstdio>
-
 #include "awq_quant.h"
 
 namespace awq {
-
-int set_error(int code, const char* msg);   // awq_capi.hip
-
 namespace {
 
 // ---- group reductions -------------------------------------------------------------------
 // Streaming kernel: the L consecutive lanes of a group (DPP inside 16-lane rows, one
 // v_permlane16_swap for L = 32).  The sum adds own + partner at every level: the pairwise
-// tree over adjacent chunks that awq_quantize_search defines.
-template <int CTRL>
-__device__ __forceinline__ float dpp_addf(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
+// tree over adjacent chunks that awq_quantize_search defines (awq_lanes.h).
 template <int L>
 struct RedGroup {
     __device__ static int imax(int v) { return grp_max<L>(v); }
     __device__ static uint32_t umax(uint32_t v) { return grp_max<L>(v); }
-    __device__ static float sum(float v) {
-        v = dpp_addf<0xB1>(v);                 // quad_perm [1,0,3,2]
-        v = dpp_addf<0x4E>(v);                 // quad_perm [2,3,0,1]
-        if (L >= 8) v = dpp_addf<0x141>(v);    // row_half_mirror
-        if (L >= 16) v = dpp_addf<0x140>(v);   // row_mirror
-        if (L >= 32) {                         // rows 0<->1, 2<->3
-            const unsigned u = __builtin_bit_cast(unsigned, v);
-            const auto p = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-            v = __builtin_bit_cast(float, (unsigned)p[0]) + __builtin_bit_cast(float, (unsigned)p[1]);
-        }
-        return v;
-    }
+    __device__ static float sum(float v) { return grp_sum<L>(v); }
 };
 // Fallback kernel: the whole wave is one group (xor butterfly = the same tree over 64 chunk
 // slots; lanes past the group's chunks add +0 and repeat the last chunk for the maxima).
 struct RedWave {
-    __device__ static int imax(int v) {
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) v = max(v, __shfl_xor(v, o, 64));
-        return v;
-    }
-    __device__ static uint32_t umax(uint32_t v) {
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-        return v;
-    }
-    __device__ static float sum(float v) {
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
-        return v;
-    }
+    __device__ static int imax(int v) { return wave_max_up(v); }
+    __device__ static uint32_t umax(uint32_t v) { return wave_max_up(v); }
+    __device__ static float sum(float v) { return wave_sum(v); }
 };
 
 // 8 values of dtype D (as fp32) -> the raw chunk the range / quantize helpers read
@@ -101,14 +69,6 @@ __device__ __forceinline__ float clip_shrink(float v, float al) {
 }
 __device__ __forceinline__ float clip_alpha(int n_grid, int i) { return (float)(n_grid - i) / (float)n_grid; }
 
-// RN_f32(a / s) from rs = RN_f32(1 / s) and one Markstein correction (awq_actsearch.hip mquot:
-// exact for fp16-valued a and s in [2^-60, 2^60], awq_selftest 1)
-__device__ __forceinline__ float clip_mquot(float a, float s, float rs) {
-    const float q0 = a * rs;
-    const float r = __builtin_fmaf(-s, q0, a);
-    return __builtin_fmaf(r, rs, q0);
-}
-
 // One candidate's loss over this lane's chunk: q (awq.py:245-248) of w', dq = fp16(fp16(q - z) *
 // fp16(scale)) (awq.py:459-539), d = RN_f32(dq / s[k]) - w, c = x_sq[k] (d d), summed in element
 // order from +0.  MQ: the quotient through the reciprocals, else the IEEE division.
@@ -136,7 +96,7 @@ __device__ __forceinline__ float chunk_loss(const Chunk<F::NW>& v, const float (
         // q - z is an integer of magnitude <= 510 (exact in fp16); the product of two fp16 values
         // is exact in fp32, so the conversion is the fp16 multiply's single rounding
         const float dq = (float)(_Float16)opaque((q - zf) * sh);
-        const float wh = MQ ? clip_mquot(dq, cs[i], rs[i]) : dq / cs[i];
+        const float wh = MQ ? mquot(dq, cs[i], rs[i]) : dq / cs[i];
         const float d = wh - w[i];
         acc = acc + xs[i] * (d * d);
     }
@@ -390,14 +350,6 @@ __global__ __launch_bounds__(64) void clip_group_kernel(ClipArgs a, int gs) {
     if (lane == 0 && a.qzeros) a.qzeros[W] = (int32_t)zword;
 }
 
-bool aligned(const void* p, size_t n) { return ((uintptr_t)p % n) == 0; }
-
-int fail(int code, const char* fmt, long long x = 0, long long y = 0) {
-    char buf[320];
-    snprintf(buf, sizeof buf, fmt, x, y);
-    return set_error(code, buf);
-}
-
 template <typename F>
 void launch_clip(bool stream_ok, int gs, int bits, int sym, unsigned grid, hipStream_t st, const ClipArgs& a) {
 #define AWQ_CLIP_GS(B, S)                                                                                    \
@@ -433,15 +385,15 @@ extern "C" int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, 
                                         int32_t* qzeros, uint16_t* scales, int32_t* best_idx, float* group_loss,
                                         int64_t loss_stride, void* stream) {
     set_error(AWQ_OK, "");
-    const int64_t gs = group_size32;
-    if (bits != 4 && bits != 8) return fail(AWQ_EINVAL, "Unsupported bit width: %lld. Supported: 4, 8.", bits);
+    const long long gs = group_size32, R = rows, KK = K;   // (long long: the messages' %lld)
+    if (bits != 4 && bits != 8) return fail(AWQ_EINVAL, "Unsupported bit width: %d. Supported: 4, 8.", bits);
     if (gs <= 0) return fail(AWQ_EINVAL, "Group size must be a positive integer: %lld", gs);
-    if (rows < 0 || K < 0) return fail(AWQ_EINVAL, "negative shape (%lld, %lld)", rows, K);
+    if (rows < 0 || K < 0) return fail(AWQ_EINVAL, "negative shape (%lld, %lld)", R, KK);
     if (dtype == AWQ_DTYPE_F64) return fail(AWQ_EUNSUPPORTED, "awq_quantize_clip_scaled: fp64 weights are not supported");
     if (dtype < AWQ_DTYPE_BF16 || dtype > AWQ_DTYPE_F32)
-        return fail(AWQ_EINVAL, "awq_quantize_clip_scaled: dtype must be bf16, fp16 or fp32 (got code %lld)", dtype);
+        return fail(AWQ_EINVAL, "awq_quantize_clip_scaled: dtype must be bf16, fp16 or fp32 (got code %d)", dtype);
     if (n_grid < 1 || n_candidates < 1 || n_candidates > n_grid)
-        return fail(AWQ_EINVAL, "clip search needs 1 <= n_candidates (%lld) <= n_grid (%lld)", n_candidates, n_grid);
+        return fail(AWQ_EINVAL, "clip search needs 1 <= n_candidates (%d) <= n_grid (%d)", n_candidates, n_grid);
     if (!qweight && !qzeros && !scales && !best_idx && !group_loss) return fail(AWQ_EINVAL, "no output requested");
     if (rows == 0 || K == 0) return AWQ_OK;
     if (!w || !col_scale || !x_sq) return fail(AWQ_EINVAL, "null input");
@@ -449,12 +401,12 @@ extern "C" int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, 
         return fail(AWQ_EUNSUPPORTED, "awq_quantize_clip_scaled: group_size %lld > 512 is not supported", gs);
     if (gs < 8 || (gs & (gs - 1)) != 0 || K % gs != 0)
         return fail(AWQ_EUNSUPPORTED,
-                    "awq_quantize_clip_scaled: group_size %lld must be a power of two in [8, 512] dividing K = %lld", gs, K);
-    const int64_t G = K / gs;
+                    "awq_quantize_clip_scaled: group_size %lld must be a power of two in [8, 512] dividing K = %lld", gs, KK);
+    const long long G = K / gs;
     if (G > (int64_t)0x7FFFFFFF / rows || K > ((int64_t)1 << 40) / rows)
-        return fail(AWQ_EUNSUPPORTED, "awq_quantize_clip_scaled: %lld x %lld groups exceed the kernels' range", rows, G);
+        return fail(AWQ_EUNSUPPORTED, "awq_quantize_clip_scaled: %lld x %lld groups exceed the kernels' range", R, G);
     if (group_loss && loss_stride < rows * G)
-        return fail(AWQ_EINVAL, "group_loss needs loss_stride (%lld) >= rows * G (%lld)", loss_stride, rows * G);
+        return fail(AWQ_EINVAL, "group_loss needs loss_stride (%lld) >= rows * G (%lld)", (long long)loss_stride, R * G);
     const size_t esz = dtype == AWQ_DTYPE_F32 ? 4 : 2;
     if (!aligned(w, esz) || !aligned(col_scale, 4) || !aligned(col_rscale, 4) || !aligned(x_sq, 4) ||
         !aligned(qweight, 4) || !aligned(qzeros, 4) || !aligned(scales, 2) || !aligned(best_idx, 4) ||
@@ -467,7 +419,7 @@ extern "C" int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, 
                            (!col_rscale || aligned(col_rscale, 16));
     const int64_t blocks = stream_ok ? tiles : rows * WPR;
     if (blocks > (int64_t)0x7FFFFFFF)
-        return fail(AWQ_EUNSUPPORTED, "awq_quantize_clip_scaled: %lld x %lld is beyond one launch's grid", rows, K);
+        return fail(AWQ_EUNSUPPORTED, "awq_quantize_clip_scaled: %lld x %lld is beyond one launch's grid", R, KK);
     ClipArgs a;
     a.w = w; a.cs = col_scale; a.rs = col_rscale; a.xs = x_sq;
     a.qweight = qweight; a.qzeros = qzeros; a.scales = scales; a.best_idx = best_idx;
@@ -483,10 +435,5 @@ extern "C" int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, 
         else launch_clip<FmtF32>(stream_ok, (int)gs, bits, symmetric, (unsigned)blocks, st, a);
         e = hipPeekAtLastError();
     }
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "awq clip kernels: %s", hipGetErrorString(e));
-        return set_error(AWQ_EHIP, buf);
-    }
-    return AWQ_OK;
+    return hip_status(e, "awq clip kernels");
 }

@@ -13,6 +13,7 @@
 //
 // Every element-wise op follows the reference recipe for the weight dtype D (refmath:
 // fp32 math, RNE to D after each op); the scale table is computed in fp64.
+#include "awq_quant.h"
 #include "awq_refmath.h"
 
 namespace awq {
@@ -20,114 +21,37 @@ namespace {
 
 using namespace refmath;
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-
-// ---- hardware-conversion arithmetic for bf16 / fp16 weights (the streaming kernel's
-// verified identities, awq_fast.hip): same results as refmath, ~4x fewer VALU ----
-__device__ __forceinline__ float opq(float a) {   // value barrier: no f16 narrowing / mixlo fusion
-    asm volatile("" : "+v"(a));
-    return a;
-}
-__device__ __forceinline__ float hw_rn_bf16(float a) {   // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
-    b2 h = __builtin_convertvector((f2){0.0f, a}, b2);
-    return __builtin_bit_cast(float, h);
-}
-__device__ __forceinline__ float hw_rn_f16(float a) { return (float)(_Float16)opq(a); }   // v_cvt_f16_f32: RNE
-
-// RN_f32(1/s) for a bf16-valued s: v_rcp_f32 + one Newton step, correctly rounded for every
-// bf16 s < 2^126 (awq_selftest checks all of them against IEEE 1/s); IEEE division beyond
-__device__ __forceinline__ float recip_bf16(float s) {
-    if (__builtin_expect(!(s < 0x1p126f), 0)) return 1.0f / s;
-    const float r0 = __builtin_amdgcn_rcpf(s);
-    const float e = __builtin_fmaf(-s, r0, 1.0f);
-    return __builtin_fmaf(r0, e, r0);
-}
-
+// ---- hardware-conversion arithmetic for bf16 / fp16 / fp32 weights: the streaming kernel's
+// verified identities (awq_quant.h FmtBF16 / FmtF16Search / FmtF32): same results as refmath,
+// ~4x fewer VALU.  What the search adds: RN(d / qr) from the run-time reciprocal rq = RN_f32(1 / qr)
+// (qmax - qmin is a kernel argument here, a template constant there) ----
 template <int DT> struct HwFmt;
-template <> struct HwFmt<AWQ_DTYPE_BF16> {
-    __device__ static float lo() { return __uint_as_float(0x2EDC0000u); }   // RN_bf16(1e-10)
-    // RN(d / qr) for bf16 d, qr in {15, 255}: d * RN(1/qr) (the same exhaustive identity)
+template <> struct HwFmt<AWQ_DTYPE_BF16> : FmtBF16 {
+    // RN(d / qr) for bf16 d, qr in {15, 255}: d * RN(1/qr) (exhaustive, oracle/verify_recip.c)
     __device__ static float scale(float d, float qr, float rq) {
         (void)qr;
-        return hw_rn_bf16(d * rq);
-    }
-    __device__ static float recip(float s) { return recip_bf16(s); }
-    // RN(x / s) for any s >= RN(1e-10) incl. inf / NaN (r = 0 / NaN carries them)
-    __device__ static float quot_any(float x, float s, float r) {
-        (void)s;
-        return hw_rn_bf16(x * r);
-    }
-    __device__ static float rn(float a) { return hw_rn_bf16(a); }
-    // RN(x / s) = RN_bf16(x * RN_f32(1/s)) for bf16 x and bf16 s >= RN_bf16(1e-10)
-    // (exhaustive, oracle/verify_recip.c)
-    __device__ static float quot(float x, float s, float r) {
-        (void)s;
-        return hw_rn_bf16(x * r);
+        return rn(d * rq);
     }
 };
-// AWQ_F16_PARAMS_FAST = 0: the fp16 group parameters by IEEE divisions (as csrc/awq_quant.h)
-#ifndef AWQ_F16_PARAMS_FAST
-#define AWQ_F16_PARAMS_FAST 1
-#endif
-// rcp + one Newton step: IEEE 1/s for every positive finite fp16 s (awq_selftest 2)
-__device__ __forceinline__ float recip_f16(float s) {
-    if (__builtin_expect(!(s > 0.0f && s < __builtin_inff()), 0)) return 1.0f / s;
-    const float r0 = __builtin_amdgcn_rcpf(s);
-    const float e = __builtin_fmaf(-s, r0, 1.0f);
-    return __builtin_fmaf(r0, e, r0);
-}
-template <> struct HwFmt<AWQ_DTYPE_F16> {
-    __device__ static float lo() { return 0.0f; }                           // RN_f16(1e-10) = 0
+template <> struct HwFmt<AWQ_DTYPE_F16> : FmtF16Search {
 #if AWQ_F16_PARAMS_FAST
     // RN_f16(d / qr) == RN_f16(d * RN_f32(1/qr)), every non-negative fp16 d incl. inf
     // (oracle/verify_recip.c f16scale)
     __device__ static float scale(float d, float qr, float rq) {
         (void)qr;
-        return hw_rn_f16(opq(hw_rn_f16(d)) * rq);
-    }
-    __device__ static float recip(float s) { return recip_f16(s); }
-    // the Markstein quotient for a positive finite s (verify_recip f16m), IEEE otherwise
-    __device__ static float quot_any(float x, float s, float r) {
-        if (__builtin_expect(!(s > 0.0f && s < __builtin_inff()), 0)) return hw_rn_f16(opq(x) / s);
-        return quot(x, s, r);
+        return rn(opaque(rn(d)) * rq);
     }
 #else
     __device__ static float scale(float d, float qr, float rq) {   // IEEE: d may be inf (Markstein would NaN)
         (void)rq;
-        return hw_rn_f16(opq(d) / qr);
-    }
-    __device__ static float recip(float s) { return 1.0f / s; }
-    __device__ static float quot_any(float x, float s, float r) {          // IEEE: s may be 0 / inf / NaN
-        (void)r;
-        return hw_rn_f16(opq(x) / s);
+        return rn(opaque(d) / qr);
     }
 #endif
-    __device__ static float rn(float a) { return hw_rn_f16(a); }
-    // Markstein-corrected quotient, exact for every fp16 x and positive finite fp16 s
-    // (oracle/verify_recip.c f16m)
-    __device__ static float quot(float x, float s, float r) {
-        const float q0 = x * r;
-        const float e = __builtin_fmaf(-s, q0, x);
-        return hw_rn_f16(__builtin_fmaf(e, r, q0));
-    }
 };
-// fp32 weights: every op is the fp32 op itself, x / s the IEEE division
-template <> struct HwFmt<AWQ_DTYPE_F32> {
-    __device__ static float lo() { return 1e-10f; }
+template <> struct HwFmt<AWQ_DTYPE_F32> : FmtF32 {
     __device__ static float scale(float d, float qr, float rq) {
         (void)rq;
         return d / qr;
-    }
-    __device__ static float recip(float s) { return 1.0f / s; }
-    __device__ static float quot_any(float x, float s, float r) {
-        (void)r;
-        return x / s;
-    }
-    __device__ static float rn(float a) { return a; }
-    __device__ static float quot(float x, float s, float r) {
-        (void)r;
-        return x / s;
     }
 };
 
@@ -147,7 +71,7 @@ __device__ __forceinline__ void hw_group_params(float mn, float mx, int nan, int
         mx = a;
     }
     float s = H::scale(H::rn(mx - mn), (float)(qmax - qmin), rq);   // awq.py:202
-    if (!(s != s) && s < H::lo()) s = H::lo();                        // awq.py:205
+    if (!(s != s) && s < H::lo_clamp()) s = H::lo_clamp();          // awq.py:205
     const float r = H::recip(s);
     float z = 0.0f;
     if (!sym)                                                 // awq.py:210-211
@@ -156,134 +80,6 @@ __device__ __forceinline__ void hw_group_params(float mn, float mx, int nan, int
     z_out = z;
     r_out = r;
 }
-
-// Reductions over the lpg consecutive lanes of a group (lpg a power of two <= 64), every
-// lane getting the result: DPP inside 16-lane rows (quad perms, half-row / row mirrors —
-// after the earlier steps these pair exactly the lanes an xor butterfly pairs), permlane
-// swaps across rows.  fmin/fmax skip NaN (NaN is tracked separately); the sum adds
-// own + partner at every level like the xor butterfly (the canonical tree, include/awq_hip.h).
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-__device__ __forceinline__ int dppi(int v) {
-    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true);
-}
-// the two 16-lane rows (or 32-lane halves) of a pair, swapped: lane l sees {its pair's
-// first half, its pair's second half} whichever half it is in, so combining p.x and p.y
-// symmetrically (min, max, or, +) gives every lane f(own, partner) exactly
-__device__ __forceinline__ void swap16(unsigned u, unsigned& a, unsigned& b) {
-    const auto p = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    a = p[0];
-    b = p[1];
-}
-__device__ __forceinline__ void swap32(unsigned u, unsigned& a, unsigned& b) {
-    const auto p = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    a = p[0];
-    b = p[1];
-}
-__device__ __forceinline__ float fbits(unsigned u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ unsigned ubits(float f) { return __builtin_bit_cast(unsigned, f); }
-
-template <bool ROW32>
-__device__ __forceinline__ void minmax_cross(float& mn, float& mx, int& nan) {
-    unsigned a, b;
-    if (ROW32) swap32(ubits(mn), a, b); else swap16(ubits(mn), a, b);
-    mn = __builtin_amdgcn_fmed3f(fbits(a), fbits(b), -__builtin_inff());
-    if (ROW32) swap32(ubits(mx), a, b); else swap16(ubits(mx), a, b);
-    mx = __builtin_amdgcn_fmed3f(fbits(a), fbits(b), __builtin_inff());
-    if (ROW32) swap32((unsigned)nan, a, b); else swap16((unsigned)nan, a, b);
-    nan = (int)(a | b);
-}
-
-// min(a, b) / max(a, b) as v_med3 against -inf / +inf: no NaN-quieting of the DPP-moved
-// operand (fminf / fmaxf need it in IEEE mode); NaN is tracked on the side, so no operand is
-// NaN whenever the result is used
-__device__ __forceinline__ float min2(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, -__builtin_inff()); }
-__device__ __forceinline__ float max2(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, __builtin_inff()); }
-
-__device__ __forceinline__ void grp_minmax(float& mn, float& mx, int& nan, int lpg) {
-    if (lpg >= 2) { mn = min2(mn, dppf<0xB1>(mn)); mx = max2(mx, dppf<0xB1>(mx)); nan |= dppi<0xB1>(nan); }
-    if (lpg >= 4) { mn = min2(mn, dppf<0x4E>(mn)); mx = max2(mx, dppf<0x4E>(mx)); nan |= dppi<0x4E>(nan); }
-    if (lpg >= 8) { mn = min2(mn, dppf<0x141>(mn)); mx = max2(mx, dppf<0x141>(mx)); nan |= dppi<0x141>(nan); }
-    if (lpg >= 16) { mn = min2(mn, dppf<0x140>(mn)); mx = max2(mx, dppf<0x140>(mx)); nan |= dppi<0x140>(nan); }
-    if (lpg >= 32) minmax_cross<false>(mn, mx, nan);
-    if (lpg >= 64) minmax_cross<true>(mn, mx, nan);
-}
-
-// v_min_f32 / v_max_f32 with the partner lane's operand through DPP, one instruction per step
-// (the compiler turns min2 / max2 into v_min / v_max behind a canonicalising v_max x, x and a
-// separate v_mov_dpp: three).  The s_nop covers the VALU-write -> DPP-read wait states (the
-// operand may have been written by the instruction just before).  No NaN reaches these (the
-// weights' NaN flag is tracked on the side), and the sign of a zero extreme cannot change the
-// scale or zero point.
-#define AWQ_DPP_MINMAX(NAME, OP, CTRL)                                                                   \
-    __device__ __forceinline__ float NAME(float v) {                                                    \
-        float r;                                                                                        \
-        asm("s_nop 1\n\t" OP "_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(v)); \
-        return r;                                                                                       \
-    }
-AWQ_DPP_MINMAX(min_xor1, "v_min_f32", "quad_perm:[1,0,3,2]")
-AWQ_DPP_MINMAX(max_xor1, "v_max_f32", "quad_perm:[1,0,3,2]")
-AWQ_DPP_MINMAX(min_xor2, "v_min_f32", "quad_perm:[2,3,0,1]")
-AWQ_DPP_MINMAX(max_xor2, "v_max_f32", "quad_perm:[2,3,0,1]")
-AWQ_DPP_MINMAX(min_hmir, "v_min_f32", "row_half_mirror")
-AWQ_DPP_MINMAX(max_hmir, "v_max_f32", "row_half_mirror")
-AWQ_DPP_MINMAX(min_mir, "v_min_f32", "row_mirror")
-AWQ_DPP_MINMAX(max_mir, "v_max_f32", "row_mirror")
-#undef AWQ_DPP_MINMAX
-#ifndef AWQ_ACT_DPP_MINMAX
-#define AWQ_ACT_DPP_MINMAX 1
-#endif
-
-// the group min / max alone (the weights' NaN flag is reduced once per item: grp_or)
-__device__ __forceinline__ void grp_minmax_nn(float& mn, float& mx, int lpg) {
-#if AWQ_ACT_DPP_MINMAX
-    if (lpg >= 2) { mn = min_xor1(mn); mx = max_xor1(mx); }
-    if (lpg >= 4) { mn = min_xor2(mn); mx = max_xor2(mx); }
-    if (lpg >= 8) { mn = min_hmir(mn); mx = max_hmir(mx); }
-    if (lpg >= 16) { mn = min_mir(mn); mx = max_mir(mx); }
-    // the compiler's hazard tracking does not see into the asm: wait states before the cross-row
-    // swaps below read its results
-    if (lpg >= 32) asm volatile("s_nop 1" : "+v"(mn), "+v"(mx));
-#else
-    if (lpg >= 2) { mn = min2(mn, dppf<0xB1>(mn)); mx = max2(mx, dppf<0xB1>(mx)); }
-    if (lpg >= 4) { mn = min2(mn, dppf<0x4E>(mn)); mx = max2(mx, dppf<0x4E>(mx)); }
-    if (lpg >= 8) { mn = min2(mn, dppf<0x141>(mn)); mx = max2(mx, dppf<0x141>(mx)); }
-    if (lpg >= 16) { mn = min2(mn, dppf<0x140>(mn)); mx = max2(mx, dppf<0x140>(mx)); }
-#endif
-    if (lpg >= 32) {
-        int dummy = 0;
-        minmax_cross<false>(mn, mx, dummy);
-    }
-    if (lpg >= 64) {
-        int dummy = 0;
-        minmax_cross<true>(mn, mx, dummy);
-    }
-}
-__device__ __forceinline__ int grp_or(int v, int lpg) {
-    if (lpg >= 2) v |= dppi<0xB1>(v);
-    if (lpg >= 4) v |= dppi<0x4E>(v);
-    if (lpg >= 8) v |= dppi<0x141>(v);
-    if (lpg >= 16) v |= dppi<0x140>(v);
-    unsigned a, b;
-    if (lpg >= 32) { swap16((unsigned)v, a, b); v = (int)(a | b); }
-    if (lpg >= 64) { swap32((unsigned)v, a, b); v = (int)(a | b); }
-    return v;
-}
-
-__device__ __forceinline__ float grp_sum(float v, int lpg) {
-    if (lpg >= 2) v = v + dppf<0xB1>(v);
-    if (lpg >= 4) v = v + dppf<0x4E>(v);
-    if (lpg >= 8) v = v + dppf<0x141>(v);
-    if (lpg >= 16) v = v + dppf<0x140>(v);
-    unsigned x, y;
-    if (lpg >= 32) { swap16(ubits(v), x, y); v = fbits(x) + fbits(y); }   // own + partner, either order
-    if (lpg >= 64) { swap32(ubits(v), x, y); v = fbits(x) + fbits(y); }
-    return v;
-}
-
 
 // Canonical fp64 summation orders (oracle/awq_oracle.c ACT_*; include/awq_hip.h): two or
 // three levels, so that a workgroup runs many short dependent chains instead of a few long
@@ -797,44 +593,7 @@ __global__ __launch_bounds__(kTabSlice) void table_norm_kernel(const double* __r
 // (awq.py:459-539), ŵ = dq / s_i (fp32), e = ŵ - w, loss = sum x_sq[k] * (e * e): each
 // lane sums its 8 elements in order, then the xor-butterfly (pairwise) tree over the
 // group's LPG lanes; part[i * stride + r * G + g] (fp32).
-// ŵ = RN_f32(dq / s) from rs = RN_f32(1 / s) with one Markstein correction: exact for every
-// fp16-valued dq and every s in [2^-60, 2^60] (awq_selftest 1: all 2^23 mantissas of s x
-// every positive finite fp16 dq, 2.7e11 pairs, against the IEEE division; the steps are
-// scale-invariant while no intermediate leaves the normal range, which this s range keeps)
-__device__ __forceinline__ float mquot(float a, float s, float rs) {
-    const float q0 = a * rs;
-    const float r = __builtin_fmaf(-s, q0, a);
-    return __builtin_fmaf(r, rs, q0);
-}
-// the same with a = the low (HI = false) or high half of a packed fp16 pair: the two products
-// with a read the fp16 value directly (v_fma_mix_f32; q0 = a * rs + (-0): the product's bits,
-// signed zeros included), the bits of mquot((float)a, s, rs)
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-template <bool HI>
-__device__ __forceinline__ float mquot_h(h2v a, float s, float rs) {
-    float q0, r;
-    const float nz = -0.0f;
-    if (HI) {
-        asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(q0) : "v"(a), "v"(rs), "v"(nz));
-        asm("v_fma_mix_f32 %0, -%1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(s), "v"(q0), "v"(a));
-    } else {
-        asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(q0) : "v"(a), "v"(rs), "v"(nz));
-        asm("v_fma_mix_f32 %0, -%1, %2, %3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(s), "v"(q0), "v"(a));
-    }
-    return __builtin_fmaf(r, rs, q0);
-}
-
-// RN_f32(a * r) with a = the low / high fp16 half (v_fma_mix_f32 with a -0 addend: the product's
-// bits, signed zeros included)
-template <bool HI>
-__device__ __forceinline__ float mprod_h(h2v a, float r) {
-    float p;
-    const float nz = -0.0f;
-    if (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(p) : "v"(a), "v"(r), "v"(nz));
-    else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(p) : "v"(a), "v"(r), "v"(nz));
-    return p;
-}
-
+// ŵ = RN_f32(dq / s) from rs = RN_f32(1 / s): mquot / mquot_h (awq_quant.h).
 // LPG: lanes per group as a constant (0 = the run-time lpg argument); SYM: symmetric;
 // EPL: elements per lane — 16 (two consecutive 8-element chunks, LPG = gs / 16 lanes per
 // group) halves the per-candidate group work per element (reductions, RTN parameters, table
@@ -983,9 +742,6 @@ __device__ __forceinline__ void lds_slot_rs(f4v (&rp)[EPL / 4], float (&rs)[EPL]
 #pragma unroll
         for (int e = 0; e < 4; ++e) rs[4 * q + e] = rp[q][e];
 }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t act_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
 
 template <int DT, int LPG, bool SYM, int EPL>
 __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict__ w, int64_t R, int64_t K, int lpg_rt,
@@ -1084,7 +840,7 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                 // v_pk_max_f16 (NaN skipped like fminf / fmaxf; NaN is tracked by nan_w)
 #pragma unroll
                 for (int j = 0; j < EPL; j += 2)
-                    wsp[j / 2] = __builtin_convertvector((f2){opq(v[j] * s[j]), opq(v[j + 1] * s[j + 1])}, h2v);
+                    wsp[j / 2] = __builtin_convertvector((f2){opaque(v[j] * s[j]), opaque(v[j + 1] * s[j + 1])}, h2v);
                 h2v a = wsp[0], b = wsp[0];
 #pragma unroll
                 for (int k = 1; k < EPL / 2; ++k) {
@@ -1190,7 +946,7 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                                     p0 = mquot_h<false>(wsp[k], cs, r);
                                     p1 = mquot_h<true>(wsp[k], cs, r);
                                 }
-                                const h2v th = __builtin_convertvector((f2){opq(p0), opq(p1)}, h2v);
+                                const h2v th = __builtin_convertvector((f2){opaque(p0), opaque(p1)}, h2v);
                                 const h2v uh = sym ? th : th + czv;
                                 const h2v q = __builtin_elementwise_min(__builtin_elementwise_max(uh + offv, lov), hiv);
                                 dqp[k] = (q - qzv) * shv;
@@ -1218,12 +974,12 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                                 for (int u2 = 0; u2 < 2; ++u2) {
                                     // fp16, every group of the wave with s < 14: the plain quotient
                                     // RN_f16(RN_f32(w' r)) (oracle/verify_recip.c f16s)
-                                    const float t = decltype(plain)::value ? hw_rn_f16(opq(ws[j + u2] * r))
+                                    const float t = decltype(plain)::value ? FmtF16Search::quot_plain(ws[j + u2], r)
                                                                            : H::quot(ws[j + u2], cs, r);
                                     uu[u2] = sym ? t : H::rn(t + cz);
                                 }
                             }
-                            const h2v uh = __builtin_convertvector((float __attribute__((ext_vector_type(2)))){uu[0], uu[1]}, h2v);
+                            const h2v uh = __builtin_convertvector((f2){uu[0], uu[1]}, h2v);
                             const h2v q = __builtin_elementwise_min(__builtin_elementwise_max(uh + offv, lov), hiv);
                             dqp[j / 2] = (q - qzv) * shv;
                         }
@@ -1243,7 +999,7 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                             const float u = sym ? t : H::rn(t + cz);
                             qq[u2] = __builtin_amdgcn_fmed3f(__builtin_rintf(u), (float)qmin, (float)qmax);
                         }
-                        dqp[j / 2] = (h2v){(_Float16)opq((qq[0] - cz) * sh), (_Float16)opq((qq[1] - cz) * sh)};
+                        dqp[j / 2] = (h2v){(_Float16)opaque((qq[0] - cz) * sh), (_Float16)opaque((qq[1] - cz) * sh)};
                     }
                 }
                 auto dqf = [&](int j) { return (float)dqp[j / 2][j & 1]; };
@@ -1254,7 +1010,7 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                     const float t = H::quot(ws[j], cs, r);
                     const float u = sym ? t : H::rn(t + cz);
                     const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(u), (float)qmin, (float)qmax);
-                    dq[j] = hw_rn_f16((q - cz) * sh);
+                    dq[j] = FmtF16Search::rn((q - cz) * sh);
                 }
                 auto dqf = [&](int j) { return dq[j]; };
 #endif
@@ -1310,7 +1066,7 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                 // than valid group leaders address past the buffer range and write nothing
                 const uint32_t off = (gl.valid && leader) ? (uint32_t)((gl.r * G + gl.g) * 4) : 0x80000000u;
                 __builtin_amdgcn_raw_buffer_store_b32(
-                    __float_as_uint(a), act_rsrc(part + (int64_t)i * stride, (uint32_t)(stride * 4)), off, 0, 0);
+                    __float_as_uint(a), rsrc(part + (int64_t)i * stride, (uint32_t)(stride * 4)), off, 0, 0);
             } else if (gl.valid && leader) {
                 part[(int64_t)i * stride + gl.r * G + gl.g] = a;
             }
@@ -1603,7 +1359,8 @@ __global__ __launch_bounds__(256) void recip_table_kernel(const float* __restric
 }
 
 // awq_selftest 1: mquot == IEEE division for every s in [1, 2) (all 2^23 mantissas) and every
-// positive finite fp16 a; counts mismatches
+// positive finite fp16 a; counts mismatches.  mquot is awq_quant.h's — the one definition the
+// loss kernels here and the clip search (awq_actclip.hip) use, so this proves what they run.
 __global__ __launch_bounds__(256) void selftest_mquot_kernel(unsigned long long* mismatches) {
     const uint32_t m = blockIdx.x * 256 + threadIdx.x;
     if (m >= (1u << 23)) return;

@@ -20,7 +20,9 @@ thread_local std::string g_err;
 thread_local awq_tuning g_tuning{};   // awq_diag.h (diagnostics build only)
 #endif
 
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+}  // namespace
+
+namespace awq {   // the host helpers awq_internal.h declares for every entry-point file
 int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -30,21 +32,19 @@ int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-
-}  // namespace
-
-namespace awq {
-int set_error(int code, const char* msg) { return fail(code, "%s", msg); }   // (awq_stream.hip)
-}  // namespace awq
-
-namespace {
-
+int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 int hip_status(hipError_t e, const char* what) {
     if (e == hipSuccess) return AWQ_OK;
     return fail(AWQ_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
-
 bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+}  // namespace awq
+
+namespace {
+
+using awq::aligned;
+using awq::fail;
+using awq::hip_status;
 
 int check_common(int64_t rows, int64_t K, int64_t group_size, int bits) {
     if (bits != 4 && bits != 8) return fail(AWQ_EINVAL, "Unsupported bit width: %d. Supported: 4, 8.", bits);

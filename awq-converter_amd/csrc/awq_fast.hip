@@ -159,28 +159,9 @@ __device__ __forceinline__ void load_tile(const char* wp, uint32_t valid, Chunk<
                 rw, (uint32_t)(j * 512 * F::kBytes + lane * 8 * F::kBytes + 16 * h), 0, AWQ_LOAD_AUX);
 }
 
-// sum over the L lanes of a group, pairwise over adjacent lanes (xor 1, xor 2, then the
-// half-row and row mirrors and the row swap pair adjacent blocks): every lane ends with the
-// same value, the tree include/awq_hip.h (awq_quantize_search) defines for the clip-search
-// error
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-template <int L>
-__device__ __forceinline__ float grp_sum(float v) {
-    v = dpp_add<0xB1>(v);                  // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);                  // quad_perm [2,3,0,1]
-    if (L >= 8) v = dpp_add<0x141>(v);     // row_half_mirror
-    if (L >= 16) v = dpp_add<0x140>(v);    // row_mirror
-    if (L >= 32) {                         // (row 2k) + (row 2k+1) on both rows
-        const auto p = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v),
-                                                        false, false);
-        v = __builtin_bit_cast(float, (unsigned)p[0]) + __builtin_bit_cast(float, (unsigned)p[1]);
-    }
-    return v;
-}
-
+// The clip-search error is summed over a group's L lanes by grp_sum<L> (awq_lanes.h: the
+// pairwise tree awq_quantize_search defines).
+//
 // The same tree for the 4 groups of this lane's loads at once, each lane keeping only the sum
 // of the group it scores (load p = lane & 3, the lane's jj): a reduce-scatter.  Pair sums (xor
 // 1) keep the two loads of this lane's parity, quad sums (xor 2) the lane's own load; the
@@ -193,10 +174,10 @@ __device__ __forceinline__ float grp_sum_scatter(const float (&e)[4]) {
     const bool b0 = lane & 1, b1 = lane & 2;
     const float m01 = b0 ? e[1] : e[0], s01 = b0 ? e[0] : e[1];
     const float m23 = b0 ? e[3] : e[2], s23 = b0 ? e[2] : e[3];
-    const float u = m01 + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s01), 0xB1, 0xF, 0xF, true));
-    const float w = m23 + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s23), 0xB1, 0xF, 0xF, true));
+    const float u = m01 + dpp_mov<0xB1>(s01);
+    const float w = m23 + dpp_mov<0xB1>(s23);
     const float m = b1 ? w : u, s = b1 ? u : w;
-    float t = m + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, true));
+    float t = m + dpp_mov<0x4E>(s);
     if (L >= 8) {   // lane ^ 4: quads 1, 3 read lane - 4 (row_ror:4), quads 0, 2 lane + 4 (row_ror:12)
         const int tb = __builtin_bit_cast(int, t);
         int x = __builtin_amdgcn_update_dpp(tb, tb, 0x124, 0xF, 0xA, false);
@@ -205,9 +186,9 @@ __device__ __forceinline__ float grp_sum_scatter(const float (&e)[4]) {
     }
     if (L >= 16) t = dpp_add<0x128>(t);    // lane ^ 8: row_ror:8
     if (L >= 32) {                         // (row 2k) + (row 2k+1) on both rows
-        const auto p = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, t), __builtin_bit_cast(unsigned, t),
-                                                        false, false);
-        t = __builtin_bit_cast(float, (unsigned)p[0]) + __builtin_bit_cast(float, (unsigned)p[1]);
+        float a, b;
+        swap16(t, a, b);
+        t = a + b;
     }
     return t;
 }

@@ -19,7 +19,6 @@
 #include "awq_quant.h"
 
 namespace awq {
-int set_error(int code, const char* msg);   // awq_capi.hip
 namespace {
 
 template <typename F>
@@ -154,7 +153,5 @@ extern "C" int awq_fold_rows(const void* w, int dtype, int64_t rows, int64_t K, 
     if (rows > ((int64_t)1 << 60) / K)         // rows * K (and its byte offsets) must fit int64
         return awq::set_error(AWQ_EINVAL, ("shape too large (" + std::to_string(rows) + ", " + std::to_string(K) + ")").c_str());
     if (!w || !row_scale || !out) return awq::set_error(AWQ_EINVAL, "null argument");
-    const hipError_t e = awq::launch_fold_rows(w, dtype, rows, K, row_scale, out, (hipStream_t)stream);
-    if (e != hipSuccess) return awq::set_error(AWQ_EHIP, (std::string("awq fold rows: ") + hipGetErrorString(e)).c_str());
-    return AWQ_OK;
+    return awq::hip_status(awq::launch_fold_rows(w, dtype, rows, K, row_scale, out, (hipStream_t)stream), "awq fold rows");
 }

@@ -184,6 +184,13 @@ inline const awq_tuning& tuning() {
 }
 #endif
 
+// host helpers of the extern "C" entry points, defined once in awq_capi.hip.  The message is the
+// calling thread's awq_last_error(); each returns the code it is given.
+int set_error(int code, const char* msg);
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int hip_status(hipError_t e, const char* what);   // AWQ_OK, or AWQ_EHIP with "<what>: <hip error string>"
+bool aligned(const void* p, size_t a);            // p is a multiple of a (a null p is)
+
 // launchers (awq_fast.hip / awq_generic.hip).  nan_code: nan_scale_code() of the call.
 hipError_t launch_fast(const awq_tensor_desc* descs_dev, const int32_t* block_tensor,
                        const awq_tensor_desc* single, int n, int64_t total_tiles, int dtype, int bits,

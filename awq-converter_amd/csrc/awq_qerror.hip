@@ -15,40 +15,15 @@
 // which the xor butterfly over a group's lanes reproduces (fp addition commutes; every partial
 // is >= +0, so the empty slots' zeros change nothing).
 #include <algorithm>
-#include <cstdio>
 
 #include "awq_quant.h"
 
 namespace awq {
-int set_error(int code, const char* msg);   // awq_capi.hip
-
 namespace {
 
 constexpr int kMaxGroup = 512;             // 64 chunk slots of 8 elements
 constexpr int kGroupBlock2 = 1024;         // groups per level-2 block (= awq_act_search_select's)
 constexpr int64_t kMaxBlocks2 = 6144 * 32; // blocks awq_act_search_select's last level takes
-
-// one step of the butterfly: add a DPP-permuted copy (every source lane valid)
-template <int CTRL, typename T>
-__device__ __forceinline__ T dpp_add(T v) {
-    return v + __builtin_bit_cast(T, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// sum over the L = GS / 8 consecutive lanes of a group, adjacent pairs first (xor 1, xor 2, the
-// half-row and row mirrors, the row swap): awq_fast.hip's grp_sum, for float and int
-template <int L, typename T>
-__device__ __forceinline__ T grp_sum(T v) {
-    static_assert(L == 4 || L == 8 || L == 16 || L == 32, "lanes per group");
-    v = dpp_add<0xB1>(v);                  // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);                  // quad_perm [2,3,0,1]
-    if (L >= 8) v = dpp_add<0x141>(v);     // row_half_mirror
-    if (L >= 16) v = dpp_add<0x140>(v);    // row_mirror
-    if (L >= 32) {                         // (row 2k) + (row 2k+1) on both rows
-        const auto p = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v),
-                                                        false, false);
-        v = __builtin_bit_cast(T, (unsigned)p[0]) + __builtin_bit_cast(T, (unsigned)p[1]);
-    }
-    return v;
-}
 
 // The statistics of one chunk's elements, accumulated in element order.
 struct Acc {
@@ -228,13 +203,6 @@ __device__ __forceinline__ float load_elem(const void* w, int64_t i) {
     return ((const float*)w)[i];
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);   // adjacent pairs first
-    return v;
-}
-
 template <int DT>
 __global__ __launch_bounds__(256) void qerror_group_kernel(const void* __restrict__ w,
                                                            const uint32_t* __restrict__ qweight,
@@ -331,14 +299,6 @@ __global__ __launch_bounds__(256) void qerror_final_kernel(const double* __restr
     }
 }
 
-bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
-int fail(int code, const char* fmt, long long a = 0, long long b = 0) {
-    char buf[256];
-    snprintf(buf, sizeof buf, fmt, a, b);
-    return set_error(code, buf);
-}
-
 int64_t level2_blocks(int64_t n_groups) { return (n_groups + kGroupBlock2 - 1) / kGroupBlock2; }
 
 // shape limits shared by both entry points: 0 = fine
@@ -389,11 +349,11 @@ extern "C" int awq_quant_error(const void* w, int dtype, int64_t rows, int64_t K
                                float* group_stats, int32_t* group_nonfinite, double* work, double* totals,
                                void* stream) {
     (void)symmetric;   // q - z = field(qweight) - field(qzeros): qmin cancels
-    if (bits != 4 && bits != 8) return fail(AWQ_EINVAL, "Unsupported bit width: %lld. Supported: 4, 8.", bits);
+    if (bits != 4 && bits != 8) return fail(AWQ_EINVAL, "Unsupported bit width: %d. Supported: 4, 8.", bits);
     if (int rc = check_shape(rows, K, group_size)) return rc;
     if (dtype == AWQ_DTYPE_F64) return fail(AWQ_EUNSUPPORTED, "awq_quant_error: fp64 weights are not supported");
     if (dtype != AWQ_DTYPE_BF16 && dtype != AWQ_DTYPE_F16 && dtype != AWQ_DTYPE_F32)
-        return fail(AWQ_EINVAL, "awq_quant_error: dtype code %lld is not a weight dtype (bf16, fp16, fp32)", dtype);
+        return fail(AWQ_EINVAL, "awq_quant_error: dtype code %d is not a weight dtype (bf16, fp16, fp32)", dtype);
     const int64_t n = rows * K;
     const int64_t G = (K + group_size - 1) / group_size, ng = rows * G;
     if (n > 0 && (!w || !qweight || !qzeros || !scales || !group_stats || !group_nonfinite))
@@ -446,10 +406,5 @@ extern "C" int awq_quant_error(const void* w, int dtype, int64_t rows, int64_t K
             e = hipPeekAtLastError();
         }
     }
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "awq quant error kernels: %s", hipGetErrorString(e));
-        return set_error(AWQ_EHIP, buf);
-    }
-    return AWQ_OK;
+    return hip_status(e, "awq quant error kernels");
 }

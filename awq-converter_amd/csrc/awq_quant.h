@@ -1,14 +1,22 @@
-// awq_quant.h — device helpers shared by the streaming kernel (awq_fast.hip) and the
-// row-segment kernel (awq_rowgroup.hip): input formats (raw-bits min/max, decoding, the
-// reference's per-op rounding and exact quotients), group parameters from a group's range
-// (awq.py:173-213), the field chain and nibble / byte packing (awq.py:215-250), fp16 scale
-// bits (awq.py:411).  Each including file gets its own copies (anonymous namespace).
+// awq_quant.h — device helpers of the quantization arithmetic, shared by six kernel files: the
+// streaming kernel (awq_fast.hip), the row-segment kernel (awq_rowgroup.hip), the error report
+// (awq_qerror.hip), the clip search (awq_actclip.hip), the scale search (awq_actsearch.hip) and
+// scale folding (awq_fold.hip).  Input formats (raw-bits min/max, decoding, the reference's
+// per-op rounding and exact quotients), group parameters from a group's range (awq.py:173-213),
+// the field chain and nibble / byte packing (awq.py:215-250), fp16 scale bits (awq.py:411).
+// Cross-lane reductions: awq_lanes.h.  Each including file gets its own copies (anonymous
+// namespace).
+//
+// Same bits, different code: where two spellings of one operation give the same bits but not the
+// same instructions, both stay here side by side, each with a comment naming its users and why
+// it exists — a kernel is never bent to the other spelling (its generated code is measured).
 #ifndef AWQ_QUANT_H
 #define AWQ_QUANT_H
 #include <cstdlib>
 #include <type_traits>
 
 #include "awq_internal.h"
+#include "awq_lanes.h"
 
 // Cache-policy bits of the input loads and the qweight / tensor_q stores (gfx950: 2 = nt).
 #define AWQ_LOAD_AUX 2
@@ -34,6 +42,7 @@ __device__ __forceinline__ f2 pk_add(f2 a, f2 b) { return a + b; }
 typedef __bf16 b2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes,
@@ -51,36 +60,12 @@ __device__ __forceinline__ float rn_bf16(float a) {
     return __builtin_bit_cast(float, h);
 }
 
-// one step of a 16-lane row reduction: max with a DPP-permuted copy (full row/bank masks,
-// every source lane valid) — LLVM folds the mov into v_max_i32_dpp (one instruction)
-template <int CTRL, typename T>
-__device__ __forceinline__ T dpp_max(T v) {   // T = int (signed max) or uint32_t (unsigned)
-    return max(v, (T)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true));
-}
-
-// max over the L = GS/8 consecutive lanes of a group; every lane of the group gets it.
-// L <= 16: DPP steps inside a row (each folds into one v_max_i32_dpp); L = 32: the group
-// spans two rows, paired by one v_permlane16_swap (gfx950).
-template <int L, typename T>
-__device__ __forceinline__ T grp_max(T v) {
-    static_assert(L == 4 || L == 8 || L == 16 || L == 32, "lanes per group");
-    v = dpp_max<0xB1>(v);                  // quad_perm [1,0,3,2]
-    v = dpp_max<0x4E>(v);                  // quad_perm [2,3,0,1]
-    if (L >= 8) v = dpp_max<0x141>(v);     // row_half_mirror
-    if (L >= 16) v = dpp_max<0x140>(v);    // row_mirror
-    if (L >= 32) {                         // rows 0<->1, 2<->3
-        const auto p = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-        v = max((T)p[0], (T)p[1]);
-    }
-    return v;
-}
-
 // value of lane J of each quad broadcast to its quad (DPP quad_perm [J,J,J,J]).  Every lane
 // c of a group with c & 3 == J holds the parameters of the group in load J, so this one
 // DPP hands them to all the group's lanes for any GS.
 template <int J>
 __device__ __forceinline__ float quad_bcast(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), J * 0x55, 0xF, 0xF, true));
+    return dpp_mov<J * 0x55>(v);
 }
 
 __device__ __forceinline__ float bcast_j(int j, float v) {   // j is a compile-time constant at every use
@@ -192,6 +177,43 @@ __device__ __forceinline__ float opaque_s(float a) {
     return a;
 }
 
+// RN_f32(a / s) from rs = RN_f32(1 / s) with one Markstein correction: exact for every
+// fp16-valued a and every s in [2^-60, 2^60] (awq_selftest 1, launch_selftest_mquot, runs THIS
+// definition — the one every kernel uses: all 2^23 mantissas of s x every positive finite fp16
+// a, 2.7e11 pairs, against the IEEE division; the steps are scale-invariant while no
+// intermediate leaves the normal range, which this s range keeps)
+__device__ __forceinline__ float mquot(float a, float s, float rs) {
+    const float q0 = a * rs;
+    const float r = __builtin_fmaf(-s, q0, a);
+    return __builtin_fmaf(r, rs, q0);
+}
+// the same with a = the low (HI = false) or high half of a packed fp16 pair: the two products
+// with a read the fp16 value directly (v_fma_mix_f32; q0 = a * rs + (-0): the product's bits,
+// signed zeros included), the bits of mquot((float)a, s, rs)
+template <bool HI>
+__device__ __forceinline__ float mquot_h(h2v a, float s, float rs) {
+    float q0, r;
+    const float nz = -0.0f;
+    if (HI) {
+        asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(q0) : "v"(a), "v"(rs), "v"(nz));
+        asm("v_fma_mix_f32 %0, -%1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(s), "v"(q0), "v"(a));
+    } else {
+        asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(q0) : "v"(a), "v"(rs), "v"(nz));
+        asm("v_fma_mix_f32 %0, -%1, %2, %3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(s), "v"(q0), "v"(a));
+    }
+    return __builtin_fmaf(r, rs, q0);
+}
+// RN_f32(a * r) with a = the low / high fp16 half (v_fma_mix_f32 with a -0 addend: the product's
+// bits, signed zeros included)
+template <bool HI>
+__device__ __forceinline__ float mprod_h(h2v a, float r) {
+    float p;
+    const float nz = -0.0f;
+    if (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(p) : "v"(a), "v"(r), "v"(nz));
+    else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(p) : "v"(a), "v"(r), "v"(nz));
+    return p;
+}
+
 // AWQ_F16_PARAMS_FAST = 0: the fp16 group parameters by IEEE divisions (scale, reciprocal, zero
 // point) as before round 6's last trims
 #ifndef AWQ_F16_PARAMS_FAST
@@ -258,6 +280,32 @@ struct FmtF16 {
     __device__ static float elem(const Chunk<1>& c, int i) {
         const uint32_t w = c.w[0][i >> 1];
         return (i & 1) ? hi(w) : lo(w);
+    }
+};
+
+// FmtF16 as the activation-aware scale search spells it (user: awq_actsearch.hip's HwFmt; same
+// bits, different code).  rn() carries the value barrier itself, where FmtF16::rn leaves it to
+// its callers, and quot() forms its first product as the plain multiply of mquot (v_mul_f32)
+// where FmtF16::quot writes fma(x, r, -0) (v_fma_f32 plus an SGPR constant, which lets the
+// streaming kernels fold the fp16 -> f32 conversions into v_fma_mix_f32).  The loss kernels'
+// generated code was measured with these spellings, the streaming kernels' with FmtF16's.
+// Static members hide, they do not override: rn, quot, quot_plain and quot_any below are the
+// search's; the inherited scale(d, qr) and as_fmt would still round with FmtF16::rn, so they are
+// deleted here (HwFmt defines the scale the search uses).
+struct FmtF16Search : FmtF16 {
+    __device__ static float scale(float d, float qr) = delete;
+    __device__ static float as_fmt(float z) = delete;
+    __device__ static float rn(float a) { return (float)(_Float16)opaque(a); }
+    __device__ static float quot(float x, float s, float r) { return rn(mquot(x, s, r)); }
+    __device__ static float quot_plain(float x, float r) { return rn(opaque(x * r)); }
+    __device__ static float quot_any(float x, float s, float r) {
+#if AWQ_F16_PARAMS_FAST
+        if (__builtin_expect(!(s > 0.0f && s < __builtin_inff()), 0)) return rn(opaque(x) / s);
+        return quot(x, s, r);
+#else
+        (void)r;
+        return rn(opaque(x) / s);                     // IEEE: s may be 0 / inf / NaN
+#endif
     }
 };
 
@@ -399,7 +447,6 @@ __device__ __forceinline__ void pack8_cvt(const float (&u)[8], uint32_t& w0, uin
 // the field rint(t) + HALF.  No NaN or inf reaches here (such groups are special).  The
 // fields' low bytes are gathered by v_perm_b32 and, at 4 bits, folded into nibbles: ≈35
 // VALU per 8 elements against ≈64 for the per-element f32 chain + v_cvt_pk_u8_f32.
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 template <int BITS, bool SYM>
 __device__ __forceinline__ void pack8_f16_plain(const uint32_t (&d)[4], const float (&r)[8], const float (&z)[8],
                                                 uint32_t& w0, uint32_t& w1) {

@@ -2,9 +2,11 @@
 // semantics: fp32 math, fp64 for fp64 inputs, round-to-nearest-even to the input dtype
 // after every op; software conversions independent of the hardware ones), shared by the
 // generic kernel (awq_generic.hip) and the activation-aware search (awq_actsearch.hip).
+// Whole-wave reductions (wave_sum / wave_min / wave_max / wave_or): awq_lanes.h.
 #pragma once
 
 #include "awq_internal.h"
+#include "awq_lanes.h"
 
 namespace awq {
 namespace refmath {
@@ -81,22 +83,6 @@ template <> struct Traits<AWQ_DTYPE_F64> {
     static __device__ S store(double v) { return v; }
 };
 
-template <typename C> __device__ __forceinline__ C wave_min(C v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { C t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-    return v;
-}
-template <typename C> __device__ __forceinline__ C wave_max(C v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { C t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_or(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ float absv(float v) { return __builtin_fabsf(v); }
 __device__ __forceinline__ double absv(double v) { return __builtin_fabs(v); }
 __device__ __forceinline__ float rnd(float v) { return __builtin_rintf(v); }
@@ -108,16 +94,6 @@ template <typename C> __device__ __forceinline__ C clampq(C v, C lo, C hi) {   /
 }
 template <typename C> __device__ __forceinline__ int32_t to_i32(C v) {         // NaN -> INT_MIN
     return (v != v) ? INT32_MIN : (int32_t)v;
-}
-
-template <typename C> __device__ __forceinline__ C wave_sum(C v) {
-    // xor butterfly with growing offsets = the pairwise tree over adjacent lanes: lanes l
-    // and l^o add the same two values, so every lane ends with the same sum
-    // (oracle_quantize_search restates this tree; the streaming kernel's 16-lane DPP
-    // reduction is the same tree's first four levels)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
-    return v;
 }
 
 // awq.py:196-213: scale and zero point of one group from its (NaN-propagated) min/max.

@@ -86,10 +86,6 @@ __device__ __forceinline__ void field8_bf16(const float (&x)[8], const float (&r
 // DPP quad / mirror steps and the row-pair swaps (wave-uniform lgP), every lane ends with
 // its block's result
 template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
-}
-template <int CTRL>
 __device__ __forceinline__ void rg_step(int& smax, uint32_t& umax, uint32_t& umin) {
     smax = max(smax, (int)dpp_mov<CTRL>((uint32_t)smax));
     umax = max(umax, dpp_mov<CTRL>(umax));

@@ -46,7 +46,7 @@ int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+using awq::aligned;
 
 struct Piece {
     int item;
@@ -577,10 +577,6 @@ void submitter_main(Pipeline* P) {
 }
 
 }  // namespace
-
-namespace awq {
-int set_error(int code, const char* msg);   // awq_capi.hip
-}
 
 extern "C" {
 

@@ -11,8 +11,8 @@ mkdir -p build/ab_$NAME ../awq_quantizer/_lib/ab
 HIPFLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt"
 /opt/rocm/bin/hipcc $HIPFLAGS "$@" -Rpass-analysis=kernel-resource-usage -c $SRC -o build/ab_$NAME/${SRC%.hip}.o 2> build/ab_$NAME/remarks.txt
 OBJS=""
-for src in awq_capi awq_fast awq_rowgroup awq_generic awq_export awq_actsearch awq_stream awq_ptfile; do
-  o=build/$src.o; b=$src.o
+for src in $(make -s --no-print-directory srcs); do   # the Makefile's SRCS
+  src=${src%.hip}; o=build/$src.o; b=$src.o
   if [ "$b" = "${SRC%.hip}.o" ]; then OBJS="$OBJS build/ab_$NAME/$b"; else OBJS="$OBJS $o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../awq_quantizer/_lib/ab/libawq_hip_$NAME.so $OBJS
