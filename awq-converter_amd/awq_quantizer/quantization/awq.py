@@ -830,6 +830,46 @@ class AWQQuantizer:
                                  out["scales"])
         return out
 
+    def import_autoawq(self, gemm: Dict[str, torch.Tensor], group_size: Optional[int] = None,
+                       symmetric: Optional[bool] = None) -> Dict[str, torch.Tensor]:
+        """The inverse of export_autoawq (include/awq_hip.h awq_import_autoawq_gemm): `gemm` holds
+        qweight int32 [in, out/8], qzeros int32 [in/group_size, out/8] and scales fp16
+        [in/group_size, out] of one linear in the AutoAWQ "GEMM" layout, on the CPU or the
+        device.  Returns a quantize_packed()-shaped dict on the device (row-major qweight /
+        qzeros / scales, bits = 4, group_size and symmetric — defaults: the quantizer's —
+        and shape = [out, in]) that dequantize_packed, quantization_error and export_autoawq
+        take unchanged.  ValueError for inconsistent shapes, RuntimeError for what the C call
+        refuses."""
+        L = self.group_size if group_size is None else int(group_size)
+        sym = self.symmetric if symmetric is None else bool(symmetric)
+        for k in ("qweight", "qzeros", "scales"):
+            if k not in gemm or gemm[k].dim() != 2:
+                raise ValueError(f"import_autoawq: '{k}' must be a 2-D tensor of the AutoAWQ GEMM layout")
+        K, N = int(gemm["qweight"].shape[0]), int(gemm["qweight"].shape[1]) * 8
+        if L <= 0 or K % L != 0:
+            raise ValueError(f"import_autoawq: in_features {K} is not a multiple of group_size {L}")
+        G = K // L
+        want = {"qweight": (K, N // 8), "qzeros": (G, N // 8), "scales": (G, N)}
+        for k, shape in want.items():
+            if tuple(gemm[k].shape) != shape:
+                raise ValueError(f"import_autoawq: {k} shape {tuple(gemm[k].shape)} != {shape} "
+                                 f"(qweight [K, N/8], qzeros [K/gs, N/8], scales [K/gs, N]; group_size {L})")
+        dev = self.compute_device()
+        src = {k: gemm[k].to(dev, torch.float16 if k == "scales" else torch.int32).contiguous() for k in want}
+        out = {"qweight": torch.empty((N, K // 8), dtype=torch.int32, device=dev),
+               "qzeros": torch.empty((N, -(-G // 8)), dtype=torch.int32, device=dev),
+               "scales": torch.empty((N, G), dtype=torch.float16, device=dev)}
+        _hip.import_autoawq_gemm(src["qweight"], src["qzeros"], src["scales"], N, K, L, 4, out["qweight"],
+                                 out["qzeros"], out["scales"])
+        out.update(bits=torch.tensor(4, dtype=torch.int32), group_size=torch.tensor(L, dtype=torch.int32),
+                   symmetric=torch.tensor(sym, dtype=torch.bool), shape=torch.tensor([N, K], dtype=torch.int64))
+        return out
+
+    def dequantize_autoawq(self, gemm: Dict[str, torch.Tensor], group_size: Optional[int] = None,
+                           symmetric: Optional[bool] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """import_autoawq, then dequantize_packed: the [out, in] weight a GEMM-layout linear holds."""
+        return self.dequantize_packed(self.import_autoawq(gemm, group_size, symmetric), dtype)
+
     def dequantize_packed(self, packed: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """Inverse of quantize_packed with the reference's dequantize arithmetic (fp16 math)."""
         shape = tuple(int(v) for v in packed["shape"].tolist())

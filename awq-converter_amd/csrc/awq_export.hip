@@ -13,16 +13,11 @@
 // qweight: one workgroup per 256 (n) x 256 (k) nibble tile, an in-register 8 x 8 nibble
 // transpose and an LDS-staged store (both HBM sides in 128-B row pieces); scales / qzeros:
 // one workgroup per 64 (n) x 32 (g) tile through LDS.  HBM-bound, about 1 B/element.
-#include "awq_internal.h"
+#include "awq_gemm_layout.h"
 
 namespace awq {
 namespace {
 
-#ifndef AWQ_EXPORT_NT_MIN
-// qweight exports of at least this many bytes are stored nontemporal (past the caches:
-// larger than half the 256 MB MALL they only evict; smaller ones gain from write-back)
-#define AWQ_EXPORT_NT_MIN (128ll << 20)
-#endif
 // qweight: a 256 (n) x 256 (k) nibble tile per workgroup.  A lane holds the words of 8
 // consecutive rows (8 nb .. 8 nb + 7) at one k-word kw, takes them in AWQ_ORDER (register
 // renaming) and transposes the 8 x 8 nibble matrix in registers (three rounds of masked
@@ -30,33 +25,12 @@ namespace {
 // lanes per 128-B row piece; 4-B loads when K % 32 != 0).  The words are staged in LDS with
 // the column XOR-swizzled by kw (2-way writes, the minimum for 64 lanes) and stored as 16-B
 // pieces of 128-B output rows.
-constexpr int kT2 = 256;                 // tile edge in nibbles (n and k)
-__device__ __forceinline__ void swapn(uint32_t& x, uint32_t& y, int sh, uint32_t mask) {
-    const uint32_t t = ((x >> sh) ^ y) & mask;
-    x ^= t << sh;
-    y ^= t;
-}
-// rows a[0..7] (8 nibbles each) -> b[j] = nibble j of every row, row AWQ_ORDER[i] at nibble i
-__device__ __forceinline__ void nibble_transpose8(const uint32_t (&a)[8], uint32_t (&b)[8]) {
-    b[0] = a[0]; b[1] = a[2]; b[2] = a[4]; b[3] = a[6];
-    b[4] = a[1]; b[5] = a[3]; b[6] = a[5]; b[7] = a[7];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) swapn(b[i], b[i + 4], 16, 0x0000FFFFu);
-#pragma unroll
-    for (int i = 0; i < 8; i += 4) {
-        swapn(b[i], b[i + 2], 8, 0x00FF00FFu);
-        swapn(b[i + 1], b[i + 3], 8, 0x00FF00FFu);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) swapn(b[i], b[i + 1], 4, 0x0F0F0F0Fu);
-}
 __device__ __forceinline__ void transpose_to_lds(const uint32_t (&a)[8], uint32_t (*ob)[kT2 / 8], int kw, int nb) {
     uint32_t b[8];
     nibble_transpose8(a, b);
 #pragma unroll
     for (int j = 0; j < 8; ++j) ob[8 * kw + j][nb ^ kw] = b[j];
 }
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <bool VEC, bool NT>
 __global__ __launch_bounds__(256) void awq_export_qweight_kernel(const int32_t* __restrict__ qweight, int64_t N,
                                                                     int64_t K, int32_t* __restrict__ qweight_t) {
@@ -134,7 +108,6 @@ __global__ __launch_bounds__(256) void awq_export_qweight_kernel(const int32_t* 
 // [g][n / 2] in LDS (column XOR-swizzled by bit 3 of g: 2-way writes, the 64-lane minimum),
 // stored as 128-B output row pieces.  qzeros: the 8 x 8 nibble transpose of the qweight tile
 // on 32 lanes (rows 8 c .. 8 c + 7 at word gw), staged and stored as row pieces.
-constexpr int kGN = 64, kGG = 32;
 __device__ __forceinline__ int gswz(int g) { return 16 * ((g >> 3) & 1); }
 template <bool VEC>
 __global__ __launch_bounds__(128) void awq_export_group_kernel(const int32_t* __restrict__ qzeros,

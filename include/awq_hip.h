@@ -261,6 +261,18 @@ int awq_export_autoawq_gemm(const int32_t* qweight, const int32_t* qzeros, const
                             int64_t K, int64_t group_size, int bits, int32_t* qweight_t, int32_t* qzeros_t,
                             uint16_t* scales_t, void* stream);
 
+/* The exact inverse of awq_export_autoawq_gemm (additive to ABI 17): from qweight_t int32
+ * [K, N/8], qzeros_t int32 [G, N/8], scales_t fp16 [G, N] (nibble i of word c = column
+ * 8c + AWQ_ORDER[i]) back to this library's row-major qweight [N, K/8], qzeros [N, ceil(G/8)]
+ * (the unused high fields of a row's last word, G % 8 != 0, are 0: import(export(p)) == p word
+ * for word) and scales [N, G].  Caller-owned device memory on the caller's stream; no
+ * allocation, no sync.  Any output may be NULL (its input is then not looked at); at least one
+ * must not be.  Pointers need 4-B (scales: 2-B) alignment; 16-B aligned ones take the wide
+ * accesses.  bits must be 4; N % 8 == 0; K % group_size == 0; the export's size limit. */
+int awq_import_autoawq_gemm(const int32_t* qweight_t, const int32_t* qzeros_t, const uint16_t* scales_t, int64_t N,
+                            int64_t K, int64_t group_size, int bits, int32_t* qweight, int32_t* qzeros,
+                            uint16_t* scales, void* stream);
+
 /* Measurement helper: copy `bytes` (multiple of 16, 16-B aligned buffers) with the
  * quantizer's memory structure (one wave per 4 KiB, 16-B nt loads/stores); bench.py
  * quotes the kernel against this copy's rate. */
