@@ -77,8 +77,7 @@ assert ctypes.sizeof(StreamItem) == 128 and ctypes.sizeof(StreamConfig) == 96
 class Tuning(ctypes.Structure):
     """Mirror of awq_tuning (csrc/awq_diag.h, diagnostics build): diagnostics / A-B controls only."""
     _fields_ = [("max_blocks", _I32), ("tiles_per_wave", _I32), ("no_rowgroup", _I32), ("rg_waves", _I32),
-                ("rg_gpt", _I32), ("gen_noreg", _I32), ("dq_words_v1", _I32),
-                ("rg_p1", _I32), ("rg_lds_full", _I32), ("rg_ldsdma", _I32), ("rg_p2reg", _I32),
+                ("rg_gpt", _I32), ("gen_noreg", _I32), ("rg_p1", _I32), ("rg_lds_full", _I32), ("rg_ldsdma", _I32), ("rg_p2reg", _I32),
                 ("rg_p1u", _I32)]
 
 # symbol -> (restype, argtypes); the CPU test suite checks every one is exported.
@@ -319,8 +318,8 @@ def tuning(**kw):
     """Diagnostics / A-B only (awq-converter_amd/csrc/awq_diag.h).  PROCESS-WIDE: inside the
     block every entry point of this module, on every thread, calls the DIAGNOSTICS build (the
     shipped libawq_hip.so has no tuning and no variant kernels).  The overrides (max_blocks,
-    tiles_per_wave, no_rowgroup, rg_waves, rg_gpt, gen_noreg, dq_words_v1, rg_p1, rg_lds_full)
-    are thread-local inside that library: they apply to launches from the calling thread only
+    tiles_per_wave, no_rowgroup, rg_waves, rg_gpt, gen_noreg (0 or 1), rg_p1, rg_lds_full and the
+    other rg_* fields) are thread-local inside that library: they apply to launches from the calling thread only
     (not, e.g., to the native stream's submitter thread).  Same results, other speed.  Restores
     the product library on exit; meant for single-threaded scripts."""
     global _lib

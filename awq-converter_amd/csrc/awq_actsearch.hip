@@ -34,19 +34,12 @@ template <> struct HwFmt<AWQ_DTYPE_BF16> : FmtBF16 {
     }
 };
 template <> struct HwFmt<AWQ_DTYPE_F16> : FmtF16Search {
-#if AWQ_F16_PARAMS_FAST
     // RN_f16(d / qr) == RN_f16(d * RN_f32(1/qr)), every non-negative fp16 d incl. inf
     // (oracle/verify_recip.c f16scale)
     __device__ static float scale(float d, float qr, float rq) {
         (void)qr;
         return rn(opaque(rn(d)) * rq);
     }
-#else
-    __device__ static float scale(float d, float qr, float rq) {   // IEEE: d may be inf (Markstein would NaN)
-        (void)rq;
-        return rn(opaque(d) / qr);
-    }
-#endif
 };
 template <> struct HwFmt<AWQ_DTYPE_F32> : FmtF32 {
     __device__ static float scale(float d, float qr, float rq) {
@@ -302,10 +295,7 @@ __device__ __forceinline__ bool group_lane(int64_t item, int64_t R, int64_t G, i
 // chain of the stage in fp64, rows
 // ascending, and the sub-block sums are added ascending per column at the end — the
 // canonical order of colsum_kernel, so part[] is bit-identical, with W read once instead of
-// twice (round 5).  (A/B builds: -DAWQ_WMEAN_FUSED=0 keeps the two-pass path.)
-#ifndef AWQ_WMEAN_FUSED
-#define AWQ_WMEAN_FUSED 1
-#endif
+// twice (round 5).
 template <int DT, int GS>
 __global__ __launch_bounds__(256) void wcolsum_fused_kernel(const void* __restrict__ w, int64_t rows, int64_t K,
                                                             double* __restrict__ part) {
@@ -599,45 +589,19 @@ __global__ __launch_bounds__(kTabSlice) void table_norm_kernel(const double* __r
 // group) halves the per-candidate group work per element (reductions, RTN parameters, table
 // checks).  The loss tree is unchanged: each chunk is summed in order, the lane adds its two
 // chunks (the tree's first pairwise level; + is commutative), grp_sum does the rest.
-// (A/B builds: -DAWQ_ACT_LDS=0 restores round 4's per-candidate register loads of the tables)
-#ifndef AWQ_ACT_LDS
-#define AWQ_ACT_LDS 1
-#endif
-// Round-6 trims of the loss kernel's per-element work (A/B builds: = 0 restores round 5's):
-//   AWQ_ACT_NAN_HOIST   the weights' NaN flag once per item, not per candidate and element
-//                       (RN(w * s) is NaN exactly when w is: s is a positive finite table entry)
-//   AWQ_ACT_NAN_RTABLE  out-of-range reciprocals as NaN: the Markstein path runs unchecked and a
-//                       wave whose loss came out NaN redoes the candidate with IEEE divisions
-//                       (no per-candidate min over the lane's reciprocals)
-//   AWQ_ACT_MIX_DQ      dq kept as packed fp16 pairs, fed to v_fma_mix_f32 in the Markstein
-//                       quotient (no fp16 -> f32 widening per element)
-#ifndef AWQ_ACT_NAN_HOIST
-#define AWQ_ACT_NAN_HOIST 1
-#endif
-#ifndef AWQ_ACT_NAN_RTABLE
-#define AWQ_ACT_NAN_RTABLE 1
-#endif
-#ifndef AWQ_ACT_MIX_DQ
-#define AWQ_ACT_MIX_DQ 1
-#endif
-//   AWQ_ACT_F16_TAIL    (round 6, later) bf16 / fp16 weights: rint, clamp and the fp16 product in
-//                       packed fp16 (two elements per instruction)
-#ifndef AWQ_ACT_F16_TAIL
-#define AWQ_ACT_F16_TAIL 1
-#endif
-//   AWQ_ACT_F16_PLAIN   fp16 weights, a wave whose group scales are all < 14: the plain quotient
-#ifndef AWQ_ACT_F16_PLAIN
-#define AWQ_ACT_F16_PLAIN 1
-#endif
-//   AWQ_ACT_F16_PACKED  fp16 weights: w' kept as packed fp16 pairs (min / max, the quotient's
-//                       operand), t and t + z in packed fp16
-#ifndef AWQ_ACT_F16_PACKED
-#define AWQ_ACT_F16_PACKED 1
-#endif
-//   AWQ_ACT_PK_F32      bf16 weights: w s, w' r and t + z as v_pk_mul_f32 / v_pk_add_f32 pairs
-#ifndef AWQ_ACT_PK_F32
-#define AWQ_ACT_PK_F32 1
-#endif
+// Round-6 trims of the loss kernel's per-element work:
+//   * the weights' NaN flag once per item, not per candidate and element (RN(w * s) is NaN
+//     exactly when w is: s is a positive finite table entry);
+//   * out-of-range reciprocals as NaN: the Markstein path runs unchecked and a wave whose loss
+//     came out NaN redoes the candidate with IEEE divisions (no per-candidate min over the
+//     lane's reciprocals);
+//   * dq kept as packed fp16 pairs, fed to v_fma_mix_f32 in the Markstein quotient (no fp16 ->
+//     f32 widening per element);
+//   * bf16 / fp16 weights: rint, clamp and the fp16 product in packed fp16 (two elements per
+//     instruction);
+//   * fp16 weights: w' kept as packed fp16 pairs (min / max, the quotient's operand), t and
+//     t + z in packed fp16; a wave whose group scales are all < 14 takes the plain quotient;
+//   * bf16 weights: w' r and t + z as v_pk_mul_f32 / v_pk_add_f32 pairs.
 // The table ring's waits are explicit: the compiler's own wait before an LDS read that may
 // alias an LDS-DMA covers every DMA in flight (vmcnt(0)), which would serialise the prefetch,
 // so the ring is read by inline-asm ds_read_b128 it does not track, with explicit lgkmcnt
@@ -657,40 +621,14 @@ __device__ __forceinline__ f4v lds_read4(uint32_t a) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t) : "v"(a), "n"(OFF) : "memory");
     return t;
 }
-// A ring slot's 2 * EPL floats: EPL scale-table entries at a (into s, waited for here) and
-// EPL reciprocals at a + 4 GSZ (left in flight in rp until lds_slot_rs).  The lgkmcnt waits
-// take the loaded registers as operands, so no use of them can be scheduled above the wait;
-// LDS reads complete in order, so lgkmcnt(EPL / 4) means the scale reads are done.
-template <int EPL, int GSZ>
-__device__ __forceinline__ void lds_slot_s(uint32_t a, float (&s)[EPL], f4v (&rp)[EPL / 4]) {
-    static_assert(EPL == 8 || EPL == 16, "8 or 16 elements per lane");
-    f4v t[EPL / 4];
-    t[0] = lds_read4<0>(a);
-    t[1] = lds_read4<16>(a);
-    if constexpr (EPL == 16) {
-        t[2] = lds_read4<32>(a);
-        t[3] = lds_read4<48>(a);
-    }
-    rp[0] = lds_read4<4 * GSZ>(a);
-    rp[1] = lds_read4<4 * GSZ + 16>(a);
-    if constexpr (EPL == 16) {
-        rp[2] = lds_read4<4 * GSZ + 32>(a);
-        rp[3] = lds_read4<4 * GSZ + 48>(a);
-        asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) : : "memory");
-    } else {
-        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(t[0]), "+v"(t[1]) : : "memory");
-    }
-#pragma unroll
-    for (int q = 0; q < EPL / 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[4 * q + e] = t[q][e];
-}
-// EPL 16 with AWQ_ACT_RS_PAIRS: the reciprocals read as (j, j + 8) pairs by ds_read2_b32 — the
-// register pairs the loss's packed ops want (the two 8-element chunks go through v_pk_fma_f32 /
-// v_pk_add_f32 side by side), instead of four ds_read_b128 and a v_mov per element to re-pair them
-#ifndef AWQ_ACT_RS_PAIRS
-#define AWQ_ACT_RS_PAIRS 1
-#endif
+// A ring slot's 2 * 16 floats (the ring serves the 16-elements-per-lane instances): 16
+// scale-table entries at a (into s, waited for here) and 16 reciprocals at a + 4 GSZ (left in
+// flight in rq until lds_slot_rs_pairs).  The lgkmcnt waits take the loaded registers as
+// operands, so no use of them can be scheduled above the wait; LDS reads complete in order, so
+// lgkmcnt(8) means the scale reads are done.  The reciprocals are read as (j, j + 8) pairs by
+// ds_read2_b32 — the register pairs the loss's packed ops want (the two 8-element chunks go
+// through v_pk_fma_f32 / v_pk_add_f32 side by side), instead of four ds_read_b128 and a v_mov
+// per element to re-pair them
 template <int O0, int O1>
 __device__ __forceinline__ f2 lds_read2(uint32_t a) {
     f2 t;
@@ -731,18 +669,6 @@ __device__ __forceinline__ void lds_slot_rs_pairs(f2 (&rq)[8], float (&rs)[16]) 
     }
 }
 
-template <int EPL>
-__device__ __forceinline__ void lds_slot_rs(f4v (&rp)[EPL / 4], float (&rs)[EPL]) {
-    if constexpr (EPL == 16)
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rp[0]), "+v"(rp[1]), "+v"(rp[2]), "+v"(rp[3]) : : "memory");
-    else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rp[0]), "+v"(rp[1]) : : "memory");
-#pragma unroll
-    for (int q = 0; q < EPL / 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) rs[4 * q + e] = rp[q][e];
-}
-
 template <int DT, int LPG, bool SYM, int EPL>
 __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict__ w, int64_t R, int64_t K, int lpg_rt,
                                                        int qmin, int qmax, const float* __restrict__ table,
@@ -750,8 +676,6 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                                                        const float* __restrict__ x_sq, float* __restrict__ part,
                                                        int64_t stride) {
     typedef HwFmt<DT> H;
-    constexpr bool kF16Packed = DT == AWQ_DTYPE_F16 && AWQ_ACT_F16_PACKED && AWQ_ACT_F16_TAIL && AWQ_ACT_MIX_DQ &&
-                                AWQ_ACT_NAN_HOIST;
     const int lpg = LPG ? LPG : lpg_rt;
     constexpr int sym = SYM ? 1 : 0;
     const int64_t G = K / (EPL * lpg);
@@ -765,11 +689,8 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
     // candidate i: wait for slot i & 1 (vmcnt(1): only candidate i - 1's loss store may still
     // be in flight — the store is a buffer store every lane issues, so the count is exact),
     // read it, issue candidate i + 1's DMA into the other slot, compute, store.
-#if AWQ_ACT_LDS
     constexpr bool kLds = LPG > 0;
-#else
-    constexpr bool kLds = false;
-#endif
+    static_assert(!kLds || EPL == 16, "the ring is read as 16 elements per lane");
     constexpr int GSZ = (LPG > 0 ? LPG : 1) * EPL;                   // group size
     constexpr int NQ = GSZ * 8 / 1024 > 0 ? GSZ * 8 / 1024 : 1;     // DMAs per candidate
     __shared__ __attribute__((aligned(16))) float ring[kLds ? 4 * 2 * 2 * GSZ : 1];
@@ -802,27 +723,20 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
         }
         if constexpr (kLds) dma(gl.g, 0, 0);
         const float* const cw = wr + (lane % lpg) * EPL;   // this lane's elements in a ring slot
-#if AWQ_ACT_NAN_HOIST
         int nan_w = 0;                                      // the group's weights hold a NaN
 #pragma unroll
         for (int j = 0; j < EPL; ++j) nan_w |= v[j] != v[j];
         nan_w = grp_or(nan_w, lpg);
-#endif
         for (int i = 0; i < n_grid; ++i) {
             float s[EPL], ws[EPL];
             float rs[EPL];
-            f4v rp[EPL / 4];
-            [[maybe_unused]] f2 rsp[8];   // (j, j + 8) reciprocal pairs
-            constexpr bool kPairs = EPL == 16 && AWQ_ACT_RS_PAIRS;
+            [[maybe_unused]] f2 rsp[8];   // (j, j + 8) reciprocal pairs (unused without rtable)
             if constexpr (kLds) {
                 // slot i & 1 holds candidate i once every operation but the previous
                 // candidate's store is done (i = 0: the item's loads and first DMA)
                 if (i == 0) vm_wait<0>();
                 else vm_wait<1>();
-                if constexpr (kPairs)
-                    lds_slot_s_pairs<GSZ>(lds_addr(cw + (i & 1) * 2 * GSZ), *(float(*)[16]) & s, rsp);
-                else
-                    lds_slot_s<EPL, GSZ>(lds_addr(cw + (i & 1) * 2 * GSZ), s, rp);   // (rp unused without rtable)
+                lds_slot_s_pairs<GSZ>(lds_addr(cw + (i & 1) * 2 * GSZ), s, rsp);
                 dma(gl.g, i + 1 < n_grid ? i + 1 : i, (i + 1) & 1);   // (last: a harmless reload)
             } else {
 #pragma unroll
@@ -832,10 +746,9 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
             // scale or zero point) with NaN tracked on the side: torch's NaN-propagating
             // min / max once combined
             float mn = __builtin_inff(), mx = -__builtin_inff();
-#if AWQ_ACT_NAN_HOIST
             const int nan = nan_w;
             [[maybe_unused]] h2v wsp[EPL / 2];   // fp16 weights: w' as packed fp16 pairs
-            if constexpr (kF16Packed) {
+            if constexpr (DT == AWQ_DTYPE_F16) {
                 // RN_f16(RN_f32(w s)) two at a time (v_cvt_pk_f16_f32), min / max as v_pk_min_f16 /
                 // v_pk_max_f16 (NaN skipped like fminf / fmaxf; NaN is tracked by nan_w)
 #pragma unroll
@@ -851,19 +764,6 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                 mx = __builtin_fmaxf((float)b.x, (float)b.y);
 #pragma unroll
                 for (int j = 0; j < EPL; ++j) ws[j] = (float)wsp[j / 2][j & 1];   // (rare paths only)
-            } else if constexpr (DT == AWQ_DTYPE_BF16 && AWQ_ACT_PK_F32 >= 2) {
-                // the products two at a time (v_pk_mul_f32: the same IEEE ops in one instruction)
-#pragma unroll
-                for (int j = 0; j < EPL; j += 2) {
-                    const f2 p = (f2){v[j], v[j + 1]} * (f2){s[j], s[j + 1]};
-                    ws[j] = H::rn(p.x);
-                    ws[j + 1] = H::rn(p.y);
-                }
-#pragma unroll
-                for (int j = 0; j < EPL; ++j) {
-                    mn = __builtin_fminf(mn, ws[j]);
-                    mx = __builtin_fmaxf(mx, ws[j]);
-                }
             } else {
 #pragma unroll
                 for (int j = 0; j < EPL; ++j) {
@@ -873,54 +773,32 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                 }
             }
             grp_minmax_nn(mn, mx, lpg);
-#else
-            int nan = 0;
-#pragma unroll
-            for (int j = 0; j < EPL; ++j) {
-                ws[j] = H::rn(v[j] * s[j]);
-                nan |= ws[j] != ws[j];
-                mn = __builtin_fminf(mn, ws[j]);
-                mx = __builtin_fmaxf(mx, ws[j]);
-            }
-            grp_minmax(mn, mx, nan, lpg);
-#endif
             if (nan) { mn = __builtin_nanf(""); mx = __builtin_nanf(""); }
             float cs, cz, r;
             hw_group_params<DT>(mn, mx, nan, qmin, qmax, sym, rq, cs, cz, r);
             float acc[EPL / 8];
 #pragma unroll
             for (int c = 0; c < EPL / 8; ++c) acc[c] = 0.0f;
-            // channel reciprocals for ŵ = dq / s (0 = outside the proven range: IEEE division)
+            // channel reciprocals for ŵ = dq / s (NaN = outside the proven range: IEEE division)
             bool mq = false;
             // (the ring's reciprocal reads are waited for with or without a reciprocal table:
             //  registers an asm load is still writing must not be reused)
-            if constexpr (kLds) {
-                if constexpr (kPairs) lds_slot_rs_pairs(rsp, *(float(*)[16]) & rs);
-                else lds_slot_rs<EPL>(rp, rs);
-            }
+            if constexpr (kLds) lds_slot_rs_pairs(rsp, rs);
             if (rtable != nullptr) {
                 if constexpr (!kLds) {
 #pragma unroll
                     for (int c = 0; c < EPL; c += 8)
                         load8<AWQ_DTYPE_F32>(rtable, (int64_t)i * K + gl.k0 + c, *(float(*)[8]) & rs[c]);
                 }
-#if AWQ_ACT_NAN_RTABLE
                 mq = true;            // out-of-range entries are NaN: checked on the losses below
-#else
-                float m = rs[0];
-#pragma unroll
-                for (int j = 1; j < EPL; ++j) m = __builtin_fminf(m, rs[j]);
-                mq = __builtin_amdgcn_ballot_w64(!(m > 0.0f)) == 0;   // wave-uniform
-#endif
             }
             if (cs > 0.0f && cs < __builtin_inff()) {
                 // finite positive scale (every group but constant fp16 / inf / NaN ones):
                 // RN(w'/s) from the group's reciprocal, hardware RNE conversions; q - z is an
                 // integer |.| <= 510, exact in fp16, so only the product is rounded
                 const float sh = (float)(_Float16)cs;
-#if AWQ_ACT_MIX_DQ
                 h2v dqp[EPL / 2];     // (q - z) * sh rounded to fp16, two per register
-                if constexpr (DT != AWQ_DTYPE_F32 && AWQ_ACT_F16_TAIL) {
+                if constexpr (DT != AWQ_DTYPE_F32) {
                     // bf16 / fp16 u: rint + clamp + (q - z) * s in packed fp16, as the clip search's
                     // chunk_err_bf16h (u exact in fp16 where it matters; oracle/verify_recip.c
                     // chain16): RN_f16(u + 1024 - qmin) clamped to [1024, 1024 + qmax - qmin], minus
@@ -929,7 +807,7 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                     const _Float16 qz1 = off + (_Float16)cz, sh1 = (_Float16)sh;
                     const h2v offv = {off, off}, lov = {(_Float16)1024, (_Float16)1024}, hiv = {hi1, hi1};
                     const h2v qzv = {qz1, qz1}, shv = {sh1, sh1};
-                    if constexpr (kF16Packed) {
+                    if constexpr (DT == AWQ_DTYPE_F16) {
                         // fp16: t from the packed w' directly (v_fma_mix_f32 reads the fp16 halves),
                         // RN_f16 two at a time, + z as v_pk_add_f16 (RN_f16 of the exact sum: f32's
                         // 24 bits >= 2 * 11 + 2 make torch's f32-then-fp16 rounding the same)
@@ -952,42 +830,25 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                                 dqp[k] = (q - qzv) * shv;
                             }
                         };
-                        if (AWQ_ACT_F16_PLAIN && __builtin_amdgcn_ballot_w64(!(cs < 14.0f)) == 0)
+                        // every group of the wave with s < 14: the plain quotient RN_f16(RN_f32(w' r))
+                        // (oracle/verify_recip.c f16s)
+                        if (__builtin_amdgcn_ballot_w64(!(cs < 14.0f)) == 0)
                             tail16(std::true_type{});
                         else
                             tail16(std::false_type{});
                     } else {
-                    auto tail = [&](auto plain) {
 #pragma unroll
                         for (int j = 0; j < EPL; j += 2) {
-                            float uu[2];
-                            if constexpr (DT == AWQ_DTYPE_BF16 && AWQ_ACT_PK_F32) {
-                                // bf16: RN(w' r) and RN(t + z) as packed pairs (v_pk_mul_f32 /
-                                // v_pk_add_f32, each half the IEEE op)
-                                const f2 p = (f2){ws[j], ws[j + 1]} * (f2){r, r};
-                                const float t0 = H::rn(p.x), t1 = H::rn(p.y);
-                                const f2 a = (f2){t0, t1} + (f2){cz, cz};
-                                uu[0] = sym ? t0 : H::rn(a.x);
-                                uu[1] = sym ? t1 : H::rn(a.y);
-                            } else {
-#pragma unroll
-                                for (int u2 = 0; u2 < 2; ++u2) {
-                                    // fp16, every group of the wave with s < 14: the plain quotient
-                                    // RN_f16(RN_f32(w' r)) (oracle/verify_recip.c f16s)
-                                    const float t = decltype(plain)::value ? FmtF16Search::quot_plain(ws[j + u2], r)
-                                                                           : H::quot(ws[j + u2], cs, r);
-                                    uu[u2] = sym ? t : H::rn(t + cz);
-                                }
-                            }
-                            const h2v uh = __builtin_convertvector((f2){uu[0], uu[1]}, h2v);
+                            // bf16: RN(w' r) and RN(t + z) as packed pairs (v_pk_mul_f32 /
+                            // v_pk_add_f32, each half the IEEE op)
+                            const f2 p = (f2){ws[j], ws[j + 1]} * (f2){r, r};
+                            const float t0 = H::rn(p.x), t1 = H::rn(p.y);
+                            const f2 a = (f2){t0, t1} + (f2){cz, cz};
+                            const float u0 = sym ? t0 : H::rn(a.x), u1 = sym ? t1 : H::rn(a.y);
+                            const h2v uh = __builtin_convertvector((f2){u0, u1}, h2v);
                             const h2v q = __builtin_elementwise_min(__builtin_elementwise_max(uh + offv, lov), hiv);
                             dqp[j / 2] = (q - qzv) * shv;
                         }
-                    };
-                    if (DT == AWQ_DTYPE_F16 && AWQ_ACT_F16_PLAIN && __builtin_amdgcn_ballot_w64(!(cs < 14.0f)) == 0)
-                        tail(std::true_type{});
-                    else
-                        tail(std::false_type{});
                     }
                 } else {
 #pragma unroll
@@ -1003,17 +864,6 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                     }
                 }
                 auto dqf = [&](int j) { return (float)dqp[j / 2][j & 1]; };
-#else
-                float dq[EPL];
-#pragma unroll
-                for (int j = 0; j < EPL; ++j) {
-                    const float t = H::quot(ws[j], cs, r);
-                    const float u = sym ? t : H::rn(t + cz);
-                    const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(u), (float)qmin, (float)qmax);
-                    dq[j] = FmtF16Search::rn((q - cz) * sh);
-                }
-                auto dqf = [&](int j) { return dq[j]; };
-#endif
                 auto ieee = [&]() {
 #pragma unroll
                     for (int c = 0; c < EPL / 8; ++c) acc[c] = 0.0f;
@@ -1026,23 +876,17 @@ __global__ __launch_bounds__(256, 3) void act_loss_kernel(const void* __restrict
                 if (mq) {
 #pragma unroll
                     for (int j = 0; j < EPL; ++j) {
-#if AWQ_ACT_MIX_DQ
                         const float w_hat = (j & 1) ? mquot_h<true>(dqp[j / 2], s[j], rs[j])
                                                     : mquot_h<false>(dqp[j / 2], s[j], rs[j]);
-#else
-                        const float w_hat = mquot(dqf(j), s[j], rs[j]);
-#endif
                         const float e = w_hat - v[j];
                         acc[j / 8] = acc[j / 8] + h[j] * (e * e);
                     }
-#if AWQ_ACT_NAN_RTABLE
                     // a NaN loss: an out-of-range reciprocal (NaN), or a NaN / inf statistic —
                     // the wave redoes the candidate with IEEE divisions (same bits in range)
                     bool bad = false;
 #pragma unroll
                     for (int c = 0; c < EPL / 8; ++c) bad |= acc[c] != acc[c];
                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) ieee();
-#endif
                 } else {
                     ieee();
                 }
@@ -1286,7 +1130,7 @@ hipError_t launch_act_stats(const void* x, int dtype, int64_t T, int64_t K, doub
 hipError_t launch_weight_colsum(const void* w, int dtype, int64_t R, int64_t K, int64_t L, float* gmax,
                                 double* part, hipStream_t stream) {
     const int64_t nb = (R + kRowBlock - 1) / kRowBlock;
-    if (AWQ_WMEAN_FUSED && (L == 32 || L == 64 || L == 128 || L == 256) && K % L == 0 && (uintptr_t)w % 16 == 0) {
+    if ((L == 32 || L == 64 || L == 128 || L == 256) && K % L == 0 && (uintptr_t)w % 16 == 0) {
         const dim3 gf((unsigned)(K / L), (unsigned)nb);
 #define AWQ_WCF(G) AWQ_DT_SWITCH(dtype, hipLaunchKernelGGL((wcolsum_fused_kernel<D, G>), gf, dim3(256), 0, stream, w, R, K, part))
         switch (L) {
@@ -1348,14 +1192,13 @@ hipError_t launch_scale_table(const float* x_mean, const float* w_mean, int64_t 
 }
 
 // rtable[i] = RN_f32(1 / table[i]) inside [2^-60, 2^60] (mquot's proven range), else a NaN
-// (AWQ_ACT_NAN_RTABLE: a quotient through it is NaN, which sends its wave to the IEEE division;
-// 0 in the round-5 encoding, checked per wave and candidate)
+// (a quotient through it is NaN, which sends its wave to the IEEE division)
 __global__ __launch_bounds__(256) void recip_table_kernel(const float* __restrict__ table, int64_t n,
                                                           float* __restrict__ rtable) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float s = table[i];
-    rtable[i] = (s >= 0x1p-60f && s <= 0x1p60f) ? 1.0f / s : (AWQ_ACT_NAN_RTABLE ? __builtin_nanf("") : 0.0f);
+    rtable[i] = (s >= 0x1p-60f && s <= 0x1p60f) ? 1.0f / s : __builtin_nanf("");
 }
 
 // awq_selftest 1: mquot == IEEE division for every s in [1, 2) (all 2^23 mantissas) and every

@@ -93,7 +93,7 @@ int awq_set_tuning(const awq_tuning* t) {
         return AWQ_OK;
     }
     if (t->max_blocks < 0 || t->tiles_per_wave < 0 || t->rg_waves < 0 || t->rg_waves > 2 || t->rg_gpt < 0 ||
-        t->rg_gpt > 64 || t->rg_gpt % 8 != 0)
+        t->rg_gpt > 64 || t->rg_gpt % 8 != 0 || t->gen_noreg < 0 || t->gen_noreg > 1)
         return fail(AWQ_EINVAL, "bad tuning values");
     g_tuning = *t;
     return AWQ_OK;

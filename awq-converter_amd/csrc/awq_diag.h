@@ -2,8 +2,10 @@
  * awq_diag.h — diagnostics / A-B measurement controls, compiled ONLY into the diagnostics
  * build libawq_hip_diag.so (`make -C awq-converter_amd/csrc diag`, -DAWQ_DIAG), which
  * scripts/ and the variant tests load explicitly.  The shipped libawq_hip.so has one path
- * per shape: no awq_set_tuning symbol, none of the A/B kernel variants, the measured
- * defaults below compiled in.
+ * per shape: no awq_set_tuning symbol, the measured defaults below compiled in.  What is left
+ * here: grid caps, the forced generic kernel and strided fp64 span, and the row-segment kernel's
+ * run-time variants.  Variants that lost their A/B (the dequantize kernels of rounds 2-6, the
+ * fp64 register span) are no longer built.
  *
  * Every setting gives the same bits as the default (the GPU tests check that); only speed
  * differs.  Thread-local: it applies to launches made from the calling thread.
@@ -24,13 +26,7 @@ typedef struct awq_tuning {
     int32_t rg_waves;        /* 1 or 2: waves per row-segment tile (0 = cost model) */
     int32_t rg_gpt;          /* 8..64, multiple of 8: groups per row-segment tile (0 = cost model) */
     int32_t gen_noreg;       /* fp64 RTN: 0 the LDS span (any gs whose span fits 16 KiB), 1 the
-                                strided span, 2 the register span at gs 64 / 128 (A/B) */
-    int32_t dq_words_v1;     /* packed dequantize kernel: 0 the default, 1 the round-2 word kernel
-                                (per-thread stores), 2 / 3 LDS-staged words with / without
-                                XCD-contiguous blocks, 4 / 5 four-output lanes without / with,
-                                6 / 7 batched four-output lanes (4 / 8 per lane), 8 / 9 the
-                                same in XCD runs; 10 / 11 2 / 1 per lane in XCD runs of 4
-                                blocks, 12 2 per lane without runs, 13 2 per lane in runs of 8 */
+                                strided span (how tests reach it on LDS-span shapes); others rejected */
     int32_t rg_p1;           /* row-segment pass 1: 0 / 1 by groups (2^k lanes per group, DPP
                                 merges), 2 evenly split runs (NT / groups lanes per group, LDS
                                 merges, parameters by one lane per group) */

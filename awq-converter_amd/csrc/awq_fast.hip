@@ -193,32 +193,9 @@ __device__ __forceinline__ float grp_sum_scatter(const float (&e)[4]) {
     return t;
 }
 
-// AWQ_SEARCH_FMA_MIX = 0: the round-5 error chain (A/B builds, scripts/build_variant.sh)
-#ifndef AWQ_SEARCH_FMA_MIX
-#define AWQ_SEARCH_FMA_MIX 1
-#endif
-#ifndef AWQ_SEARCH_S_LATE
-#define AWQ_SEARCH_S_LATE 1
-#endif
-// AWQ_SEARCH_F16_PACKED = 0: fp16 search always through the Markstein f32 chain
-#ifndef AWQ_SEARCH_F16_PACKED
-#define AWQ_SEARCH_F16_PACKED 1
-#endif
-// AWQ_SEARCH_BF16_HALF = 0: bf16 search's integer steps in f32 (chunk_err) instead of packed fp16
-#ifndef AWQ_SEARCH_BF16_HALF
-#define AWQ_SEARCH_BF16_HALF 1
-#endif
-// AWQ_SEARCH_PK_F32 = 0: the bf16 chain's products and + z as plain f32 ops (compiler's choice)
-#ifndef AWQ_SEARCH_PK_F32
-#define AWQ_SEARCH_PK_F32 1
-#endif
 // waves per SIMD the search instances are compiled for (the VGPR budget: 4 -> 128, 5 -> 96, 6 -> 80)
 #ifndef AWQ_SEARCH_MIN_WAVES
 #define AWQ_SEARCH_MIN_WAVES 4
-#endif
-// AWQ_SEARCH_SCATTER = 0: per-load group sums (grp_sum) and per-load special-scale ballots
-#ifndef AWQ_SEARCH_SCATTER
-#define AWQ_SEARCH_SCATTER 1
 #endif
 // Squared error of this lane's 8-element chunk of a group for one candidate (r, z, s) —
 // quantize (awq.py:245-248), dequantize the reference's way (fp16(fp16(q - z) * fp16(s)),
@@ -230,7 +207,6 @@ __device__ __forceinline__ float chunk_err(const Chunk<F::NW>& v, float r, float
     constexpr float QMAX = SYM ? (float)((1 << (BITS - 1)) - 1) : (float)((1 << BITS) - 1);
     const float zf = F::as_fmt(z);
     float acc = 0.0f;
-#if AWQ_SEARCH_FMA_MIX
     // element pairs: the two fp16 products packed by one v_cvt_pk_f16_f32 (RNE), then x - dq as
     // v_fma_mix_f32(dq_f16, -1, x) on each half — an exact product and one rounding, i.e. the
     // subtraction's bits, with no fp16 -> f32 widening instruction
@@ -260,24 +236,6 @@ __device__ __forceinline__ float chunk_err(const Chunk<F::NW>& v, float r, float
         acc = acc + d0 * d0;
         acc = acc + d1 * d1;
     }
-#else
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float x = F::elem(v, i);
-        float q;
-        if (__builtin_expect(special, 0)) {
-            const float t = F::rn(opaque(x) / s);
-            const float rr = __builtin_rintf(SYM ? t : F::rn(t + zf));
-            q = __builtin_isnan(rr) ? rr : __builtin_fminf(__builtin_fmaxf(rr, QMIN), QMAX);
-        } else {
-            const float t = F::quot(x, s, r);
-            q = __builtin_fminf(__builtin_fmaxf(__builtin_rintf(SYM ? t : F::rn(t + zf)), QMIN), QMAX);
-        }
-        const float dq = (float)(_Float16)((q - zf) * sh);
-        const float d = x - dq;
-        acc = acc + d * d;
-    }
-#endif
     return acc;
 }
 
@@ -314,13 +272,9 @@ __device__ __forceinline__ float chunk_err_f16p(const Chunk<1>& v, float r, uint
     for (int i = 0; i < 4; ++i) {
         const uint32_t w = v.w[0][i];
         const float x0 = FmtF16::lo(w), x1 = FmtF16::hi(w);
-#if AWQ_SEARCH_PK_F32
         f2 p = pk_mul(f2{x0, x1}, f2{r, r});     // one v_pk_mul_f32; the barrier keeps it f32-rounded
         asm volatile("" : "+v"(p));
         const h2v t = __builtin_convertvector(p, h2v);                                     // RN_f16(RN_f32(x r))
-#else
-        const h2v t = __builtin_convertvector((f2){opaque(x0 * r), opaque(x1 * r)}, h2v);   // RN_f16(RN_f32(x r))
-#endif
         const h2v u = SYM ? t : t + zz;                                                    // RN_f16(t + z)
         const h2v q = __builtin_elementwise_min(__builtin_elementwise_max(u + off, lo), hi);   // 1024 + q - qmin
         const h2v dq = (q - qz) * ss;                                                      // RN_f16((q - z) s)
@@ -360,17 +314,12 @@ __device__ __forceinline__ float chunk_err_bf16h(const Chunk<1>& v, float r, flo
     for (int i = 0; i < 4; ++i) {
         const uint32_t w = v.w[0][i];
         const float x0 = FmtBF16::lo(w), x1 = FmtBF16::hi(w);
-#if AWQ_SEARCH_PK_F32
         // the pair's product and + z as one v_pk_mul_f32 / v_pk_add_f32 each (the same IEEE ops;
         // two plain VOP2 ops only cost one slot when they dual-issue, ~11 % of the time here)
         const f2 p = pk_mul(f2{x0, x1}, f2{r, r});
         const float t0 = rn_bf16(p.x), t1 = rn_bf16(p.y);
         const f2 a = SYM ? f2{t0, t1} : pk_add(f2{t0, t1}, f2{z, z});
         const float u0 = SYM ? t0 : rn_bf16(a.x), u1 = SYM ? t1 : rn_bf16(a.y);
-#else
-        const float t0 = rn_bf16(x0 * r), t1 = rn_bf16(x1 * r);
-        const float u0 = SYM ? t0 : rn_bf16(t0 + z), u1 = SYM ? t1 : rn_bf16(t1 + z);
-#endif
         const h2v u = __builtin_convertvector((f2){u0, u1}, h2v);
         const h2v q = __builtin_elementwise_min(__builtin_elementwise_max(u + off, lo), hi);
         const h2v dq = (q - qz) * ss;
@@ -386,7 +335,7 @@ __device__ __forceinline__ float chunk_err_bf16h(const Chunk<1>& v, float r, flo
 // Opt-in clip search (include/awq_hip.h awq_quantize_search) inside the streaming kernel:
 // candidates alpha_i = (n_grid - i) / n_grid shrink [mn, mx]; lane (grp, ch) evaluates the
 // candidate's parameters for its parameter group (the one in load ch & 3), the L lanes of a
-// group score each of its 4 loads' groups (8 elements per lane, grp_sum), and the smallest
+// group score each of its 4 loads' groups (8 elements per lane, grp_sum_scatter), and the smallest
 // error (ties: the earlier candidate; NaN never wins) picks the group's final [mn, mx].
 // RN(v * alpha) as torch evaluates it (fp32 product, then one rounding to the dtype); the
 // barrier stops the fp16 product from becoming a single-rounding v_mad_mixlo_f16
@@ -409,22 +358,18 @@ __device__ __forceinline__ float search_alpha(int n_grid, int i, float rn) {
 template <typename F, int BITS, bool SYM, int GS>
 __device__ __forceinline__ void search_range(const Chunk<F::NW> (&v)[4], float& gmn, float& gmx, bool gnan, int n_grid,
                                           int n_cand) {
-    [[maybe_unused]] const int jj = threadIdx.x & 3;
     const float rn = 1.0f / (float)n_grid;
-    constexpr bool kLateS = AWQ_SEARCH_S_LATE && std::is_same<F, FmtBF16>::value;
     float best = __builtin_inff();
     int bi = 0;
     for (int i = 0; i < n_cand; ++i) {
         const float al = search_alpha(n_grid, i, rn);
         const GroupParams cp = params_from_range<F, BITS, SYM>(shrink<F>(gmn, al), shrink<F>(gmx, al));
         const float csh = F::dq_scale(cp.s);
-#if AWQ_SEARCH_SCATTER
         // one wave-wide test per candidate: any group of the tile with a 0 / inf / NaN scale sends
         // all four loads through the per-lane special-aware chain (equal bits on the other lanes)
         const bool any_special = __builtin_amdgcn_ballot_w64(!F::fast(cp.r)) != 0;
         // fp16: every scale of the wave < 14 -> the packed plain chain (chunk_err_f16p)
-        const bool plain16 = AWQ_SEARCH_F16_PACKED && std::is_same<F, FmtF16>::value &&
-                             __builtin_amdgcn_ballot_w64(!F::plain_ok(cp.s)) == 0;
+        const bool plain16 = std::is_same<F, FmtF16>::value && __builtin_amdgcn_ballot_w64(!F::plain_ok(cp.s)) == 0;
         // the packed chains' fp16 operands, once per lane (a few instructions; unused in the
         // waves that take another chain)
         uint32_t w1 = 0, w2 = 0;
@@ -443,10 +388,10 @@ __device__ __forceinline__ void search_range(const Chunk<F::NW> (&v)[4], float& 
                 if (plain16) e[j] = chunk_err_f16p<BITS, SYM>(v[j], rj, bcast_u(j, w1), bcast_u(j, w2));
                 else e[j] = chunk_err<F, BITS, SYM>(v[j], rj, SYM ? 0.0f : bcast_j(j, cp.z), bcast_j(j, cp.s),
                                                     bcast_j(j, csh), false);
-            } else if constexpr (std::is_same<F, FmtBF16>::value && AWQ_SEARCH_BF16_HALF) {
+            } else if constexpr (std::is_same<F, FmtBF16>::value) {
                 e[j] = chunk_err_bf16h<BITS, SYM>(v[j], rj, SYM ? 0.0f : bcast_j(j, cp.z), bcast_u(j, w1));
             } else {
-                e[j] = chunk_err<F, BITS, SYM>(v[j], rj, SYM ? 0.0f : bcast_j(j, cp.z), kLateS ? 0.0f : bcast_j(j, cp.s),
+                e[j] = chunk_err<F, BITS, SYM>(v[j], rj, SYM ? 0.0f : bcast_j(j, cp.z), bcast_j(j, cp.s),
                                                bcast_j(j, csh), false);
             }
         }
@@ -455,35 +400,6 @@ __device__ __forceinline__ void search_range(const Chunk<F::NW> (&v)[4], float& 
             best = ej;
             bi = i;
         }
-#else
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float rj = bcast_j(j, cp.r);
-            const float zj = SYM ? 0.0f : bcast_j(j, cp.z);
-            const float hj = bcast_j(j, csh);
-            const bool special = !F::fast(rj);
-            float e;
-            // (the scale itself only feeds the exact division of a 0 / inf / NaN scale: broadcast
-            //  in that rare wave only)
-            if constexpr (kLateS) {
-                // bf16: the common path's quotient is x * RN(1/s) (r alone); the scale itself only
-                // feeds the exact division of a 0 / inf / NaN scale — broadcast in that rare wave
-                if (__builtin_expect(__ballot(special) != 0, 0))
-                    e = chunk_err<F, BITS, SYM>(v[j], rj, zj, bcast_j(j, cp.s), hj, special);
-                else e = chunk_err<F, BITS, SYM>(v[j], rj, zj, 0.0f, hj, false);
-            } else {   // fp16 (Markstein correction) and fp32 (IEEE division) read s on every path
-                const float sj = bcast_j(j, cp.s);
-                if (__builtin_expect(__ballot(special) != 0, 0))
-                    e = chunk_err<F, BITS, SYM>(v[j], rj, zj, sj, hj, special);
-                else e = chunk_err<F, BITS, SYM>(v[j], rj, zj, sj, hj, false);
-            }
-            e = grp_sum<GS / 8>(e);
-            if (j == jj && e < best) {
-                best = e;
-                bi = i;
-            }
-        }
-#endif
     }
     if (!gnan && bi != 0) {
         const float al = search_alpha(n_grid, bi, rn);

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void awq_generic_kernel(const void* __restrict
     }
 }
 
-// DPP lane moves (VALU, no LDS round trip) for the register span's in-row levels:
+// DPP lane moves (VALU, no LDS round trip) for the LDS span's in-row levels:
 // quad_perm [1,0,3,2] (xor 1), quad_perm [2,3,0,1] (xor 2), row_half_mirror (lane i <-> 7 - i
 // of its 8), row_mirror (i <-> 15 - i of its 16).  After xor 1 and xor 2 every lane of a quad
 // holds the quad's value, so the two mirrors finish the 8- and 16-lane levels.
@@ -194,108 +194,6 @@ __device__ __forceinline__ uint32_t dpp_u(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, false);
 }
 constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140;
-
-// The same span for fp64 RTN at group sizes 64 * LPI (64, 128): the whole span (PER groups of
-// LPI elements per lane) is loaded into registers with every load in flight at once, the
-// per-group reductions and the quantize + pack pass run on the registers (no re-read), and a
-// wave's groups are wave-uniform per register slot (slot i of every lane is in group i / LPI).
-template <int LPI, int PER>
-__global__ __launch_bounds__(256) void awq_generic_span_reg_kernel(const double* __restrict__ w, int64_t rows,
-                                                                   int64_t K, int qmin, int qmax, int sym,
-                                                                   uint32_t nan_code, int32_t* __restrict__ tensor_q,
-                                                                   uint16_t* __restrict__ scales,
-                                                                   int32_t* __restrict__ zeros,
-                                                                   int32_t* __restrict__ qweight,
-                                                                   int32_t* __restrict__ qzeros) {
-    constexpr int BITS = 32 / PER, NI = LPI * PER;
-    constexpr int64_t L = 64 * LPI;
-    constexpr uint32_t MASK = (1u << BITS) - 1u;
-    const int lane = threadIdx.x & 63;
-    const int64_t G = (K + L - 1) / L;
-    const int64_t SP = (G + PER - 1) / PER;
-    const int64_t wpr = (K + PER - 1) / PER;
-    const int64_t si = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (si >= rows * SP) return;
-    const int64_t r = si / SP, sp = si - r * SP;
-    const int64_t g0 = sp * PER;
-    const int64_t base = r * K, span0 = g0 * L;
-    double v[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {                   // zero beyond K: the reference's padding
-        const int64_t k = span0 + 64 * i + lane;
-        v[i] = (k < K) ? __builtin_nontemporal_load(w + base + k) : 0.0;
-    }
-    // lane-local min/max per group, then the PER groups' butterflies interleaved (independent
-    // chains: one shuffle latency per level instead of one per level and group); NaN by ballot
-    double mn[PER], mx[PER];
-    uint64_t nanm[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        double a = v[j * LPI], b = a;
-        int nan = a != a;
-#pragma unroll
-        for (int i = 1; i < LPI; ++i) {
-            const double t = v[j * LPI + i];
-            nan |= (t != t);
-            a = t < a ? t : a;
-            b = t > b ? t : b;
-        }
-        mn[j] = a;
-        mx[j] = b;
-        nanm[j] = __ballot(nan);
-    }
-#define AWQ_RED_LEVEL(MOVE)                                                                      \
-    _Pragma("unroll") for (int j = 0; j < PER; ++j) {                                            \
-        const double a = MOVE(mn[j]), b = MOVE(mx[j]);                                          \
-        mn[j] = a < mn[j] ? a : mn[j];                                                           \
-        mx[j] = b > mx[j] ? b : mx[j];                                                           \
-    }
-    AWQ_RED_LEVEL(dpp_d<kDppXor1>)
-    AWQ_RED_LEVEL(dpp_d<kDppXor2>)
-    AWQ_RED_LEVEL(dpp_d<kDppHalfMirror>)
-    AWQ_RED_LEVEL(dpp_d<kDppMirror>)
-#define AWQ_SHFL16(x) __shfl_xor((x), 16, 64)
-#define AWQ_SHFL32(x) __shfl_xor((x), 32, 64)
-    AWQ_RED_LEVEL(AWQ_SHFL16)
-    AWQ_RED_LEVEL(AWQ_SHFL32)
-#undef AWQ_SHFL16
-#undef AWQ_SHFL32
-#undef AWQ_RED_LEVEL
-    uint32_t zword = 0;
-    double sa[PER], za[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int nan = nanm[j] != 0;
-        double sc, z;
-        group_params<AWQ_DTYPE_F64>(nan ? NAN : mn[j], nan ? NAN : mx[j], nan, qmin, qmax, sym, sc, z);
-        sa[j] = sc;
-        za[j] = z;
-        if (g0 + j >= G) continue;                   // wave-uniform: past the row's last group
-        zword |= (((uint32_t)to_i32(z) - (uint32_t)qmin) & MASK) << (BITS * j);
-        if (lane == 0) {
-            const int64_t gi = r * G + g0 + j;
-            if (scales) scales[gi] = sc != sc ? nan_scale_pick(nan_code, nan) : sw_f32_to_f16((float)sc);
-            if (zeros) zeros[gi] = to_i32(z);
-        }
-    }
-    if (qzeros && lane == 0) qzeros[r * SP + sp] = (int32_t)zword;
-    const int sh = BITS * (lane & (PER - 1));
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int64_t k = span0 + 64 * i + lane;
-        if (span0 + 64 * i >= K) break;              // wave-uniform
-        const bool act = k < K;
-        const int32_t q = act ? to_i32(quant1<AWQ_DTYPE_F64>(v[i], sa[i / LPI], za[i / LPI], qmin, qmax)) : 0;
-        if (tensor_q && act) tensor_q[base + k] = q;
-        if (qweight) {
-            uint32_t wd = act ? (((uint32_t)q - (uint32_t)qmin) & MASK) << sh : 0u;
-            wd |= dpp_u<kDppXor1>(wd);
-            wd |= dpp_u<kDppXor2>(wd);
-            if (PER == 8) wd |= dpp_u<kDppHalfMirror>(wd);
-            if (act && (lane & (PER - 1)) == 0) qweight[r * wpr + k / PER] = (int32_t)wd;
-        }
-    }
-}
 
 // fp64 RTN for any other group size 2 <= L with the span in <= 16 KiB (4-bit: L <= 256,
 // 8-bit: L <= 512): one one-wave workgroup per span (PER groups of a row), the span staged in
@@ -612,194 +510,19 @@ __global__ __launch_bounds__(256) void awq_dequant_kernel(
     }
 }
 
-// awq_dequantize_packed for word-aligned groups (K % PER == 0, L % PER == 0; PER = 32 / bits):
-// one thread per qweight word — its PER elements share one row and one group — so one
-// division per word instead of three per element, one scale and one qzeros load per word,
-// and the PER fp32 outputs leave as 16-B stores.  Arithmetic (awq.py:459-539): q - z is an
+// awq_dequantize_packed for whole qweight words per row (K % PER == 0; PER = 32 / bits), the
+// fp32 outputs leaving as 16-B stores.  Arithmetic (awq.py:459-539): q - z is an
 // integer of at most 8 bits, exact in fp16; h * s of that integer and an fp16 scale needs
 // at most 19 significand bits, so the f32 product is exact and one hardware RNE conversion
 // to fp16 gives RN_f16(h * s) bit for bit (NaN lanes take the software conversion, which
 // keeps the payload as torch does).  Memory-bound: 0.5 B (4-bit) read + 4 B written per element.
-#ifdef AWQ_DIAG   // round-2/3 dequantize variants: A/B builds only (scripts/, make diag)
-template <int BITS>
-__global__ __launch_bounds__(256) void awq_dequant_words_kernel(
-    const int32_t* __restrict__ qweight, const uint16_t* __restrict__ scales, const int32_t* __restrict__ qzeros,
-    int64_t words, uint32_t wpr, uint32_t L, uint32_t G, uint32_t zpr, int qmin, float* __restrict__ out, float /*invL*/) {
-    constexpr int PER = 32 / BITS;
-    constexpr uint32_t MASK = (1u << BITS) - 1u;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= words) return;
-    int64_t r;
-    uint32_t c;
-    if (words <= (int64_t)0xFFFFFFFFu) {                 // 32-bit index arithmetic
-        const uint32_t r32 = (uint32_t)i / wpr;
-        r = r32;
-        c = (uint32_t)i - r32 * wpr;
-    } else {
-        r = i / wpr;
-        c = (uint32_t)(i - r * wpr);
-    }
-    const uint32_t g = (uint32_t)(((uint64_t)c * PER) / L);   // (64-bit: c * PER may pass 2^32)
-    const uint32_t wq = (uint32_t)__builtin_nontemporal_load(qweight + i);
-    const float s = (float)__builtin_bit_cast(_Float16, scales[r * G + g]);
-    const int32_t z = (int32_t)(((uint32_t)qzeros[r * zpr + g / PER] >> (BITS * (g % PER))) & MASK) + qmin;
-    float v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int32_t q = (int32_t)((wq >> (BITS * j)) & MASK) + qmin;
-        const float p = (float)(q - z) * s;
-        if (__builtin_expect(__builtin_isnan(p), 0)) {   // NaN bits of the reference's fp32 copy
-            const int64_t k = (int64_t)c * PER + j, K = (int64_t)wpr * PER, g0 = (int64_t)g * L;
-            v[j] = __uint_as_float(dq_nan_bits(sw_f32_to_f16(p), k - g0, min((int64_t)L, K - g0)));
-        } else {
-            v[j] = (float)(_Float16)p;
-        }
-    }
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    f4* o = (f4*)(out + i * PER);
-#pragma unroll
-    for (int j = 0; j < PER / 4; ++j) {
-        const f4 t = {v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
-        __builtin_nontemporal_store(t, o + j);
-    }
-}
-
-// The same, with the two memory-side fixes the round-2 PMC asked for (profiles/round2/r2as:
-// 1.15x algorithmic reads, 1.13x writes):
-//  * writes: a 4-bit thread's 8 fp32 results (32 B) went out as two 16-B stores 32 B apart,
-//    so every store instruction half-covered 2 KiB of 64-B lines; here the block's 8 KiB of
-//    results are staged in LDS and each store instruction of a wave writes 1 KiB contiguous
-//    (16 B per lane);
-//  * reads: consecutive blocks (neighbouring words of a row, which share the row's scale and
-//    qzeros lines) were dealt round-robin over the 8 XCDs, each XCD's L2 fetching the shared
-//    lines again; blocks are renumbered so each XCD takes a contiguous range of the words.
-constexpr int kDqThreads = 256;
-
-__device__ __forceinline__ uint32_t xcd_contiguous_block(uint32_t b, uint32_t nb) {
-    const uint32_t full = nb / 8u * 8u;           // blocks b are dealt to XCD b % 8
-    if (b >= full) return b;
-    return (b % 8u) * (full / 8u) + b / 8u;       // XCD x: blocks x * full/8 .. (x+1) * full/8 - 1
-}
-
-template <int BITS, bool REMAP>
-__global__ __launch_bounds__(kDqThreads) void awq_dequant_words_v2_kernel(
-    const int32_t* __restrict__ qweight, const uint16_t* __restrict__ scales, const int32_t* __restrict__ qzeros,
-    int64_t words, uint32_t wpr, uint32_t L, uint32_t G, uint32_t zpr, int qmin, float* __restrict__ out, float /*invL*/) {
-    constexpr int PER = 32 / BITS;
-    constexpr uint32_t MASK = (1u << BITS) - 1u;
-    __shared__ __attribute__((aligned(16))) float stage[kDqThreads * PER];
-    const int64_t blk = REMAP ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const int64_t w0 = blk * kDqThreads;
-    const int64_t i = w0 + threadIdx.x;
-    float v[PER];
-    if (i < words) {
-        int64_t r;
-        uint32_t c;
-        if (words <= (int64_t)0xFFFFFFFFu) {
-            const uint32_t r32 = (uint32_t)i / wpr;
-            r = r32;
-            c = (uint32_t)i - r32 * wpr;
-        } else {
-            r = i / wpr;
-            c = (uint32_t)(i - r * wpr);
-        }
-        const uint32_t g = (uint32_t)(((uint64_t)c * PER) / L);
-        const uint32_t wq = (uint32_t)__builtin_nontemporal_load(qweight + i);
-        const float s = (float)__builtin_bit_cast(_Float16, scales[r * G + g]);
-        const int32_t z = (int32_t)(((uint32_t)qzeros[r * zpr + g / PER] >> (BITS * (g % PER))) & MASK) + qmin;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int32_t q = (int32_t)((wq >> (BITS * j)) & MASK) + qmin;
-            const float p = (float)(q - z) * s;
-            if (__builtin_expect(__builtin_isnan(p), 0)) {   // NaN bits of the reference's fp32 copy
-                const int64_t k = (int64_t)c * PER + j, K = (int64_t)wpr * PER, g0 = (int64_t)g * L;
-                v[j] = __uint_as_float(dq_nan_bits(sw_f32_to_f16(p), k - g0, min((int64_t)L, K - g0)));
-            } else {
-                v[j] = (float)(_Float16)p;
-            }
-        }
-    }
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const int64_t nw = min((int64_t)kDqThreads, words - w0);       // words of this block
-    if (PER == 4 || nw < kDqThreads) {
-        // 8-bit (16 B per thread: one contiguous 1 KiB per wave instruction already) and the
-        // grid's partial last block: direct stores
-        if (i < words) {
-            f4* o = (f4*)(out + i * PER);
-#pragma unroll
-            for (int j = 0; j < PER / 4; ++j)
-                __builtin_nontemporal_store((f4){v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]}, o + j);
-        }
-        return;
-    }
-    // 4-bit: stage the block's 8 KiB, then lane t of the block stores bytes 16 t + 4 KiB h
-#pragma unroll
-    for (int j = 0; j < PER / 4; ++j)
-        *(f4*)(stage + PER * threadIdx.x + 4 * j) = (f4){v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
-    __syncthreads();
-    f4* o = (f4*)(out + w0 * PER);
-#pragma unroll
-    for (int h = 0; h < PER / 4; ++h)
-        __builtin_nontemporal_store(*(const f4*)(stage + 4 * (threadIdx.x + kDqThreads * h)),
-                                    o + threadIdx.x + kDqThreads * h);
-}
-
-// The same arithmetic with four outputs per lane: a 4-bit word is shared by two neighbouring
-// lanes (each converts one nibble half), so every lane issues exactly one 16-B store and a
-// wave's store instruction covers 1 KiB contiguous with no LDS round trip or barrier (v2's
-// staging); the word, scale and qzeros loads of the lane pair hit the same dwords.  REMAP: the
-// XCD-contiguous block order of v2.
-template <int BITS, bool REMAP>
-__global__ __launch_bounds__(256) void awq_dequant_quads_kernel(
-    const int32_t* __restrict__ qweight, const uint16_t* __restrict__ scales, const int32_t* __restrict__ qzeros,
-    int64_t words, uint32_t wpr, uint32_t L, uint32_t G, uint32_t zpr, int qmin, float* __restrict__ out, float /*invL*/) {
-    constexpr int PER = 32 / BITS;
-    constexpr int LPW = PER / 4;                        // lanes per word: 2 (4-bit), 1 (8-bit)
-    constexpr uint32_t MASK = (1u << BITS) - 1u;
-    const int64_t blk = REMAP ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const int64_t t = blk * 256 + threadIdx.x;
-    const int64_t i = t / LPW;                          // word
-    const int half = (int)(t - i * LPW);                // which 4 fields of the word
-    if (i >= words) return;
-    int64_t r;
-    uint32_t c;
-    if (words <= (int64_t)0xFFFFFFFFu) {
-        const uint32_t r32 = (uint32_t)i / wpr;
-        r = r32;
-        c = (uint32_t)i - r32 * wpr;
-    } else {
-        r = i / wpr;
-        c = (uint32_t)(i - r * wpr);
-    }
-    const uint32_t g = (uint32_t)(((uint64_t)c * PER) / L);
-    const uint32_t wq = (uint32_t)__builtin_nontemporal_load(qweight + i) >> (16 * half);
-    const float s = (float)__builtin_bit_cast(_Float16, scales[r * G + g]);
-    const int32_t z = (int32_t)(((uint32_t)qzeros[r * zpr + g / PER] >> (BITS * (g % PER))) & MASK) + qmin;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int32_t q = (int32_t)((wq >> (BITS * j)) & MASK) + qmin;
-        const float p = (float)(q - z) * s;
-        if (__builtin_expect(__builtin_isnan(p), 0)) {   // NaN bits of the reference's fp32 copy
-            const int64_t k = (int64_t)c * PER + 4 * half + j, K = (int64_t)wpr * PER, g0 = (int64_t)g * L;
-            v[j] = __uint_as_float(dq_nan_bits(sw_f32_to_f16(p), k - g0, min((int64_t)L, K - g0)));
-        } else {
-            v[j] = (float)(_Float16)p;
-        }
-    }
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store((f4){v[0], v[1], v[2], v[3]}, (f4*)(out + 4 * t));
-}
-
-#endif  // AWQ_DIAG
-
 // Batched four-output lanes: each thread converts U quads (4 outputs, one 16-B store each) of
 // its block's 256 * U consecutive quads, with every load of the U quads (qweight word, scale,
 // qzeros word) issued before the first conversion — U independent loads in flight per lane
-// instead of one, and U times fewer waves (the one-quad kernels are bound by wave turnover:
+// instead of one, and U times fewer waves (one quad per lane is bound by wave turnover:
 // one load round trip per short-lived wave).  RUN > 0: RUN consecutive blocks run on one XCD
 // (blocks are dealt round-robin over the 8 XCDs) so the scale and qzeros lines a run shares
-// are fetched by one L2 — without v2's one-range-per-XCD order, whose 8 concurrent streams
+// are fetched by one L2 — without a one-range-per-XCD order, whose 8 concurrent streams
 // sit a power-of-two distance apart.
 __device__ __forceinline__ uint32_t dq_run_block(uint32_t b, uint32_t nb, uint32_t R) {
     const uint32_t full = nb / (8u * R) * (8u * R);
@@ -906,20 +629,6 @@ __global__ __launch_bounds__(256) void awq_dequant_batch_kernel(
 template <int B> constexpr auto dq_batch4_run = awq_dequant_batch_kernel<B, 4, 4, 0>;
 template <int B> constexpr auto dq_batch4_run_q = awq_dequant_batch_kernel<B, 4, 4, 1>;
 template <int B> constexpr auto dq_batch4_run_e = awq_dequant_batch_kernel<B, 4, 4, 2>;
-constexpr int kDqDefault = 8;   // batched lanes in XCD runs: profiles/round3/dequant
-#ifdef AWQ_DIAG
-template <int B> constexpr auto dq_v2_remap = awq_dequant_words_v2_kernel<B, true>;
-template <int B> constexpr auto dq_v2_plain = awq_dequant_words_v2_kernel<B, false>;
-template <int B> constexpr auto dq_quads_plain = awq_dequant_quads_kernel<B, false>;
-template <int B> constexpr auto dq_quads_remap = awq_dequant_quads_kernel<B, true>;
-template <int B> constexpr auto dq_batch4 = awq_dequant_batch_kernel<B, 4, 0, 0>;
-template <int B> constexpr auto dq_batch8 = awq_dequant_batch_kernel<B, 8, 0, 0>;
-template <int B> constexpr auto dq_batch8_run = awq_dequant_batch_kernel<B, 8, 2, 0>;
-template <int B> constexpr auto dq_batch2_run = awq_dequant_batch_kernel<B, 2, 4, 0>;
-template <int B> constexpr auto dq_batch1_run = awq_dequant_batch_kernel<B, 1, 4, 0>;
-template <int B> constexpr auto dq_batch2 = awq_dequant_batch_kernel<B, 2, 0, 0>;
-template <int B> constexpr auto dq_batch2_run8 = awq_dequant_batch_kernel<B, 2, 8, 0>;
-#endif
 
 // Measurement helper (awq_dequant_ceiling): the batched dequantize's memory structure without its
 // arithmetic and parameter loads — per quad one 4-B nt load of the packed word (a lane pair
@@ -965,26 +674,10 @@ hipError_t launch_generic(const void* w, int dtype, int64_t rows, int64_t K, int
     const unsigned grid = grid_for(rows * ((G + per - 1) / per), 4, 256 * 16);
     const bool search = n_cand > 0;
     // fp64 spans: the LDS span wherever the span fits 16 KiB (3.2-3.7 TB/s of input at gs 64 /
-    // 128, against the register span's 1.4-2.4: profiles/round3/r3n), else the strided span.
-    // Diagnostics builds (AWQ_DIAG, tuning gen_noreg): 1 = the strided span only, 2 = the
-    // register span at gs 64 / 128
+    // 128, against a register span's 1.4-2.4: profiles/round3/r3n), else the strided span.
+    // Diagnostics builds (AWQ_DIAG, tuning gen_noreg): 1 = the strided span only
 #ifdef AWQ_DIAG
     const int f64_span = tuning().gen_noreg;
-    if (dtype == AWQ_DTYPE_F64 && !search && !s_exact && !z_exact && (L == 64 || L == 128) && f64_span == 2) {
-        const unsigned blocks = (unsigned)((rows * ((G + per - 1) / per) + 3) / 4);
-        const double* wd = (const double*)w;
-#define AWQ_SPAN_REG(LPI, PER)                                                                              \
-        hipLaunchKernelGGL((awq_generic_span_reg_kernel<LPI, PER>), dim3(blocks), dim3(256), 0, stream, wd, rows, K, \
-                           qmin, qmax, symmetric, nan_scale_code(AWQ_DTYPE_F64, symmetric, small), tensor_q,     \
-                           scales, zeros, qweight, qzeros)
-        if (L == 64) {
-            if (per == 8) AWQ_SPAN_REG(1, 8); else AWQ_SPAN_REG(1, 4);
-        } else {
-            if (per == 8) AWQ_SPAN_REG(2, 8); else AWQ_SPAN_REG(2, 4);
-        }
-#undef AWQ_SPAN_REG
-        return hipPeekAtLastError();
-    }
 #else
     constexpr int f64_span = 0;
 #endif
@@ -1070,17 +763,9 @@ hipError_t launch_dequant(const int32_t* tensor_q, const int32_t* qweight, const
         L <= 0x7FFFFFFF && G <= 0x7FFFFFFF && total / per < ((int64_t)1 << 32) - 256) {   // one thread per word
         const int64_t words = total / per;
         const uint32_t wpr = (uint32_t)(K / per), zpr = (uint32_t)((G + per - 1) / per);
-        const dim3 grid((unsigned)((words + 255) / 256)), block(256);
-        // the batched four-output lanes in XCD runs (kDqDefault = 8).  Diagnostics builds
-        // (AWQ_DIAG, awq_diag.h dq_words_v1) also reach the A/B variants: 1 round-2 word
-        // kernel, 2 / 3 LDS-staged v2 with / without XCD-contiguous blocks, 4 / 5 four-output
-        // lanes without / with XCD-contiguous blocks, 6 / 7 batched lanes (4 / 8 quads), 9 the
-        // batched lanes in XCD runs of 2 blocks
-        int v = kDqDefault;
+        const dim3 block(256);
+        // the batched four-output lanes in XCD runs: profiles/round3/dequant
         const float invL = 1.0f / (float)L;
-#ifdef AWQ_DIAG
-        if (gmode == 0 && tuning().dq_words_v1 > 0 && tuning().dq_words_v1 <= 13) v = tuning().dq_words_v1;
-#endif
 #define AWQ_DQ(KER, GRID)                                                                                   \
         do {                                                                                                \
             if (bits == 4)                                                                                  \
@@ -1090,30 +775,10 @@ hipError_t launch_dequant(const int32_t* tensor_q, const int32_t* qweight, const
                 hipLaunchKernelGGL(KER<8>, GRID, block, 0, stream, qweight, scales, qzeros, words, wpr,     \
                                    (uint32_t)L, (uint32_t)G, zpr, qmin, out, invL);                         \
         } while (0)
-        const dim3 grid_q((unsigned)((words * (per / 4) + 255) / 256));
-        const dim3 grid_b4((unsigned)((words * (per / 4) + 1023) / 1024)),
-            grid_b8((unsigned)((words * (per / 4) + 2047) / 2048));
-        switch (v) {
-#ifdef AWQ_DIAG
-        case 10: AWQ_DQ(dq_batch2_run, dim3((unsigned)((words * (per / 4) + 511) / 512))); break;
-        case 11: AWQ_DQ(dq_batch1_run, grid_q); break;
-        case 12: AWQ_DQ(dq_batch2, dim3((unsigned)((words * (per / 4) + 511) / 512))); break;
-        case 13: AWQ_DQ(dq_batch2_run8, dim3((unsigned)((words * (per / 4) + 511) / 512))); break;
-        case 6: AWQ_DQ(dq_batch4, grid_b4); break;
-        case 7: AWQ_DQ(dq_batch8, grid_b8); break;
-        case 9: AWQ_DQ(dq_batch8_run, grid_b8); break;
-        case 1: AWQ_DQ(awq_dequant_words_kernel, grid); break;
-        case 2: AWQ_DQ(dq_v2_remap, grid); break;
-        case 3: AWQ_DQ(dq_v2_plain, grid); break;
-        case 4: AWQ_DQ(dq_quads_plain, grid_q); break;
-        case 5: AWQ_DQ(dq_quads_remap, grid_q); break;
-#endif
-        default:
-            if (gmode == 0) AWQ_DQ(dq_batch4_run, grid_b4);
-            else if (gmode == 1) AWQ_DQ(dq_batch4_run_q, grid_b4);
-            else AWQ_DQ(dq_batch4_run_e, grid_b4);
-            break;
-        }
+        const dim3 grid_b4((unsigned)((words * (per / 4) + 1023) / 1024));
+        if (gmode == 0) AWQ_DQ(dq_batch4_run, grid_b4);
+        else if (gmode == 1) AWQ_DQ(dq_batch4_run_q, grid_b4);
+        else AWQ_DQ(dq_batch4_run_e, grid_b4);
 #undef AWQ_DQ
         return hipPeekAtLastError();
     }

@@ -16,14 +16,10 @@
 namespace awq {
 namespace {
 
-#ifndef AWQ_IMPORT_N_FASTEST
-// qweight grid order (A/B: scripts/build_variant.sh ... -DAWQ_IMPORT_N_FASTEST=0).  1: n tiles
-// fastest, the export's order — concurrent workgroups read neighbouring 128-B pieces of the same
-// input rows.  0: k tiles fastest — they write neighbouring pieces of the same output rows.
-// Measured (profiles/import_bench.log, interleaved runs): 1 is 3-6 % faster (Llama-3-8B lm_head
-// 103.7 vs 106.6-108.2 us, 14336 x 4096 21.0 vs 22.3 us) and meets the export's rate; 0 does not.
-#define AWQ_IMPORT_N_FASTEST 1
-#endif
+// qweight grid order: n tiles fastest, the export's order — concurrent workgroups read
+// neighbouring 128-B pieces of the same input rows.  Measured against k tiles fastest
+// (profiles/import_bench.log, interleaved runs): 3-6 % faster (Llama-3-8B lm_head 103.7 vs
+// 106.6-108.2 us, 14336 x 4096 21.0 vs 22.3 us) and meets the export's rate; the other does not.
 // qweight: a lane holds the words of 8 consecutive input rows (k = 8 kb .. 8 kb + 7) at one
 // input word column c (columns 8 c .. 8 c + 7 in AWQ_ORDER) and transposes the 8 x 8 nibble
 // matrix in registers: word m is then output word (row 8 c + m, k-word kb).  Loads: 16 B per
@@ -40,11 +36,7 @@ template <bool VEC, bool NT>
 __global__ __launch_bounds__(256) void awq_import_qweight_kernel(const int32_t* __restrict__ qweight_t, int64_t N,
                                                                     int64_t K, int32_t* __restrict__ qweight) {
     __shared__ uint32_t ob[kT2][kT2 / 8];                 // [n in tile][output word column], swizzled
-#if AWQ_IMPORT_N_FASTEST
     const int64_t n0 = (int64_t)blockIdx.x * kT2, k0 = (int64_t)blockIdx.y * kT2;
-#else
-    const int64_t k0 = (int64_t)blockIdx.x * kT2, n0 = (int64_t)blockIdx.y * kT2;
-#endif
     const int64_t wpr = K / 8, wpr_t = N / 8;
     const int t = threadIdx.x;
     if constexpr (VEC) {
@@ -208,12 +200,8 @@ hipError_t launch_import_gemm(const int32_t* qweight_t, const int32_t* qzeros_t,
     // the export's size limit (its grid.y bound on K), and the same bound on this grid's y (N)
     if ((K + kT2 - 1) / kT2 > 65535 || (N + kT2 - 1) / kT2 > 65535) return hipErrorInvalidConfiguration;
     if (qweight) {
-#if AWQ_IMPORT_N_FASTEST
         // n tiles fastest: concurrent workgroups read neighbouring pieces of the same input rows
         const dim3 grid((unsigned)((N + kT2 - 1) / kT2), (unsigned)((K + kT2 - 1) / kT2));
-#else
-        const dim3 grid((unsigned)((K + kT2 - 1) / kT2), (unsigned)((N + kT2 - 1) / kT2));
-#endif
         const bool vec = N % 32 == 0 && ((uintptr_t)qweight_t & 15) == 0;
         const bool nt = N * K / 2 >= (int64_t)AWQ_EXPORT_NT_MIN;
         auto kern = vec ? (nt ? awq_import_qweight_kernel<true, true> : awq_import_qweight_kernel<true, false>)

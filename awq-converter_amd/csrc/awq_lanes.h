@@ -157,14 +157,9 @@ AWQ_DPP_MINMAX(max_hmir, "v_max_f32", "row_half_mirror")
 AWQ_DPP_MINMAX(min_mir, "v_min_f32", "row_mirror")
 AWQ_DPP_MINMAX(max_mir, "v_max_f32", "row_mirror")
 #undef AWQ_DPP_MINMAX
-// (A/B builds: -DAWQ_ACT_DPP_MINMAX=0 takes the compiler's three-instruction steps)
-#ifndef AWQ_ACT_DPP_MINMAX
-#define AWQ_ACT_DPP_MINMAX 1
-#endif
 
 // the group min / max alone (the weights' NaN flag is reduced once per item: grp_or)
 __device__ __forceinline__ void grp_minmax_nn(float& mn, float& mx, int lpg) {
-#if AWQ_ACT_DPP_MINMAX
     if (lpg >= 2) { mn = min_xor1(mn); mx = max_xor1(mx); }
     if (lpg >= 4) { mn = min_xor2(mn); mx = max_xor2(mx); }
     if (lpg >= 8) { mn = min_hmir(mn); mx = max_hmir(mx); }
@@ -172,12 +167,6 @@ __device__ __forceinline__ void grp_minmax_nn(float& mn, float& mx, int lpg) {
     // the compiler's hazard tracking does not see into the asm: wait states before the cross-row
     // swaps below read its results
     if (lpg >= 32) asm volatile("s_nop 1" : "+v"(mn), "+v"(mx));
-#else
-    if (lpg >= 2) { mn = min2(mn, dpp_mov<0xB1>(mn)); mx = max2(mx, dpp_mov<0xB1>(mx)); }
-    if (lpg >= 4) { mn = min2(mn, dpp_mov<0x4E>(mn)); mx = max2(mx, dpp_mov<0x4E>(mx)); }
-    if (lpg >= 8) { mn = min2(mn, dpp_mov<0x141>(mn)); mx = max2(mx, dpp_mov<0x141>(mx)); }
-    if (lpg >= 16) { mn = min2(mn, dpp_mov<0x140>(mn)); mx = max2(mx, dpp_mov<0x140>(mx)); }
-#endif
     int dummy = 0;
     if (lpg >= 32) minmax_cross<false>(mn, mx, dummy);
     if (lpg >= 64) minmax_cross<true>(mn, mx, dummy);

@@ -214,11 +214,6 @@ __device__ __forceinline__ float mprod_h(h2v a, float r) {
     return p;
 }
 
-// AWQ_F16_PARAMS_FAST = 0: the fp16 group parameters by IEEE divisions (scale, reciprocal, zero
-// point) as before round 6's last trims
-#ifndef AWQ_F16_PARAMS_FAST
-#define AWQ_F16_PARAMS_FAST 1
-#endif
 struct FmtF16 {
     static constexpr int NW = 1, kBytes = 2;
     static constexpr bool kWide = false;
@@ -244,7 +239,6 @@ struct FmtF16 {
         // RN_f32 first, as verified: a fused fma -> f16 (v_fma_mixlo_f16) rounds once
         return rn(opaque(__builtin_fmaf(e, r, q0)));
     }
-#if AWQ_F16_PARAMS_FAST
     // RN_f16(d / qr) == RN_f16(d * RN_f32(1/qr)) for every non-negative fp16 d, inf included, and
     // qr = 2^bits - 1 (oracle/verify_recip.c f16scale); d * (1/qr) folds to a multiply by a constant
     __device__ static float scale(float d, float qr) { return rn(opaque(rn(d)) * (1.0f / qr)); }
@@ -257,15 +251,6 @@ struct FmtF16 {
         if (__builtin_expect(!(s > 0.0f && s < __builtin_inff()), 0)) return rn(opaque(x) / s);
         return quot(x, s, r);
     }
-#else
-    __device__ static float scale(float d, float qr) { return rn(opaque(rn(d)) / qr); }   // IEEE division
-    __device__ static float lo_clamp() { return 0.0f; }                            // RN_f16(1e-10) = 0
-    __device__ static float recip(float s) { return 1.0f / s; }
-    __device__ static float quot_any(float x, float s, float r) {
-        (void)r;
-        return rn(opaque(x) / s);
-    }
-#endif
     // s = 0 (constant group: the fp16 clamp min is 0), inf or NaN -> exact special path
     __device__ static bool fast(float r) { return r > 0.0f && r < __builtin_inff(); }
     // The plain RN_f16(RN_f32(x * RN_f32(1/s))) misses RN_f16(x / s) only for scales
@@ -289,23 +274,18 @@ struct FmtF16 {
 // where FmtF16::quot writes fma(x, r, -0) (v_fma_f32 plus an SGPR constant, which lets the
 // streaming kernels fold the fp16 -> f32 conversions into v_fma_mix_f32).  The loss kernels'
 // generated code was measured with these spellings, the streaming kernels' with FmtF16's.
-// Static members hide, they do not override: rn, quot, quot_plain and quot_any below are the
-// search's; the inherited scale(d, qr) and as_fmt would still round with FmtF16::rn, so they are
-// deleted here (HwFmt defines the scale the search uses).
+// Static members hide, they do not override: rn, quot and quot_any below are the search's; the
+// inherited scale(d, qr), as_fmt and quot_plain would still round with FmtF16::rn, so they are
+// deleted here (HwFmt defines the scale the search uses; its plain quotient is mprod_h).
 struct FmtF16Search : FmtF16 {
     __device__ static float scale(float d, float qr) = delete;
     __device__ static float as_fmt(float z) = delete;
+    __device__ static float quot_plain(float x, float r) = delete;
     __device__ static float rn(float a) { return (float)(_Float16)opaque(a); }
     __device__ static float quot(float x, float s, float r) { return rn(mquot(x, s, r)); }
-    __device__ static float quot_plain(float x, float r) { return rn(opaque(x * r)); }
     __device__ static float quot_any(float x, float s, float r) {
-#if AWQ_F16_PARAMS_FAST
         if (__builtin_expect(!(s > 0.0f && s < __builtin_inff()), 0)) return rn(opaque(x) / s);
         return quot(x, s, r);
-#else
-        (void)r;
-        return rn(opaque(x) / s);                     // IEEE: s may be 0 / inf / NaN
-#endif
     }
 };
 

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """dequantize_packed (awq_dequant_batch_kernel) against its measured ceiling, interleaved in one
-process: the product kernel, diagnostics-build variants (tuning dq_words_v1) and
-awq_dequant_ceiling (the same 1 : 8 read : write structure without arithmetic or parameter
-loads) on the same footprint, `--rounds` rounds of `--iters` launches each; medians per case.
+process: the product kernel and awq_dequant_ceiling (the same 1 : 8 read : write structure
+without arithmetic or parameter loads) on the same footprint, `--rounds` rounds of `--iters`
+launches each; medians per case.
 Default: the Llama-3-8B lm_head, 128256 x 4096, gs 128, 4-bit (2.1 GB of fp32 output, past the
 256 MiB Infinity Cache).
 
-  python scripts/dq_ceiling_bench.py --variants 0,10,11
+  python scripts/dq_ceiling_bench.py --rounds 5
 """
 import argparse
 import json
@@ -39,7 +39,6 @@ def main():
     ap.add_argument("--group-size", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--variants", default="", help="diagnostics-build dq_words_v1 values (0 = its default)")
     a = ap.parse_args()
     torch.manual_seed(0)
     x = (torch.randn(a.rows, a.K, device="cuda") * 0.02).bfloat16()
@@ -59,11 +58,6 @@ def main():
 
     cases = {"product": product,
              "ceiling": lambda: _hip.dequant_ceiling(p["qweight"], out, stream)}
-    for v in [int(t) for t in a.variants.split(",") if t != ""]:
-        def variant(v=v):
-            with _hip.tuning(dq_words_v1=v):
-                _hip.dequantize_packed(p["qweight"], p["qzeros"], p["scales"], rows, K, L, 4, False, out)
-        cases[f"diag_v{v}"] = variant
     same = {}
     for name, fn in cases.items():     # warm-up + bits check of every dequantize case
         fn()

@@ -38,10 +38,7 @@ def main():
                     help="stream this long (awq_stream_ceiling) before every timed loop: the clocks of a busy "
                          "chip (bench.py's ceiling probe does the same; an idle GPU's first ~5 ms run slower, "
                          "profiles/round6/r6h)")
-    ap.add_argument("--dq-variants", default="1,3,6,7,8,9", help="--dq-ab: tuning dq_words_v1 values to time")
     ap.add_argument("--lib", default="", help="load this in-tree build instead of _lib/libawq_hip.so (A/B of builds)")
-    ap.add_argument("--dq-ab", action="store_true", help="--dequant: also the round-2 word kernel (tuning dq_words_v1), "
-                                                          "interleaved, 3 rounds")
     args = ap.parse_args()
     from awq_quantizer import _hip
     if args.lib:
@@ -131,28 +128,20 @@ def one(args, _hip, dev, shape, name, gs, generic, tun=None):
 
         def dq():
             _hip.dequantize_packed(qw, qz, sc, R, K, gs, args.bits, False, out)
-        variants = tuple(int(v) for v in args.dq_variants.split(",")) if args.dq_ab else (0,)
-        ref = None
-        for rnd in range(3 if args.dq_ab else 1):
-            for v in variants:
-                with (_hip.tuning(dq_words_v1=v) if v else contextlib.nullcontext()):
-                    for _ in range(3):
-                        dq()
-                    settle(args, _hip, dev)
-                    a.record()
-                    for _ in range(args.iters):
-                        dq()
-                    b.record()
-                    torch.cuda.synchronize()
-                if ref is None:
-                    ref = out.clone()
-                same = bool(torch.equal(out.view(torch.int32), ref.view(torch.int32)))
-                us = a.elapsed_time(b) / args.iters * 1e3
-                algo = out.numel() * 4 + sum(t.numel() * t.element_size() for t in (qw, qz, sc))
-                print(json.dumps({"op": "dequantize_packed", "lib": os.path.basename(args.lib) if args.lib else "libawq_hip.so", "kernel": ["default", "words_v1", "words_v2_xcd", "words_v2", "quads", "quads_xcd", "batch4", "batch8", "batch4_run4", "batch8_run2"][v], "round": rnd,
-                                  "shape": [R, K], "group_size": gs, "bits": args.bits, "same_bits": same,
-                                  "us": round(us, 1), "algorithmic_GBs": round(algo / us / 1e3, 1),
-                                  "frac_8TBs": round(algo / us / 1e3 / 8000, 3)}), flush=True)
+        for _ in range(3):
+            dq()
+        settle(args, _hip, dev)
+        a.record()
+        for _ in range(args.iters):
+            dq()
+        b.record()
+        torch.cuda.synchronize()
+        us = a.elapsed_time(b) / args.iters * 1e3
+        algo = out.numel() * 4 + sum(t.numel() * t.element_size() for t in (qw, qz, sc))
+        print(json.dumps({"op": "dequantize_packed", "lib": os.path.basename(args.lib) if args.lib else "libawq_hip.so",
+                          "kernel": "default", "shape": [R, K], "group_size": gs, "bits": args.bits,
+                          "us": round(us, 1), "algorithmic_GBs": round(algo / us / 1e3, 1),
+                          "frac_8TBs": round(algo / us / 1e3 / 8000, 3)}), flush=True)
 
 
 if __name__ == "__main__":

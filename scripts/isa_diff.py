@@ -7,7 +7,9 @@ For every .hip file of the csrc Makefile's SRCS, compiles the file as it stands 
 tree and as it stood at REV (exported with `git archive` into a scratch directory) with the
 Makefile's HIPFLAGS plus `--cuda-device-only -S`, once plain and once with -DAWQ_DIAG, and
 compares the two assembly texts after dropping comment lines, .file / .ident / .loc lines and
-lines that name the per-source hash symbol __hip_cuid_*.  Exit status 0 = every file identical:
+lines that name the per-source hash symbol __hip_cuid_*, and after taking the function's ordinal
+out of local labels (removing a kernel renumbers the labels of every later one; its own lines
+still show as removed).  Exit status 0 = every file identical:
 the bar for a refactor that must not change a kernel.  Needs only hipcc, no GPU.
 
 --keep DIR keeps the assembly (DIR/REV-ish/..., DIR/head/...) and reuses REV's if it is already
@@ -51,6 +53,13 @@ def normalize(path):
                 continue
             if re.match(r"\.(file|ident|loc)\b", s):
                 continue
+            # local labels carry the function's ordinal in the file (.LBB<f>_<block>, .Lfunc_end<f>):
+            # removing a kernel renumbers every later one, no code changes (a label's loop comment,
+            # padded to a column, goes too)
+            if s.startswith(".LBB"):
+                line = line.split(";")[0]
+            line = re.sub(r"\b(L?BB)\d+_(\d+)", r"\1_\2", line)
+            line = re.sub(r"(\.Lfunc_(?:begin|end))\d+", r"\1", line)
             out.append(line.rstrip())
     return out
 

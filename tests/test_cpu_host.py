@@ -46,6 +46,19 @@ def test_product_library_has_no_diagnostics_entry_points():
     assert "os.environ" not in src.replace('os.environ.get("AWQ_DIST_BACKEND"', "")
 
 
+def test_diag_tuning_rejects_a_retired_fp64_span():
+    """gen_noreg selects the fp64 span: 0 the LDS span, 1 the strided one; the register span (2) is
+    gone, and awq_set_tuning says so instead of silently taking the default."""
+    from awq_quantizer import _hip
+    diag = _hip.load_diag_library()
+    for v, rc in ((0, 0), (1, 0), (2, -1), (-1, -1)):
+        t = _hip.Tuning(gen_noreg=v)
+        assert (diag.awq_set_tuning(ctypes.byref(t)) == 0) == (rc == 0), v
+    assert diag.awq_set_tuning(None) == 0
+    assert not hasattr(_hip.Tuning(), "dq_words_v1")
+    assert ctypes.sizeof(_hip.Tuning) == 11 * 4
+
+
 def test_library_is_gfx950_code_object():
     from awq_quantizer import _hip
     data = open(_hip.LIB_PATH, "rb").read()

@@ -6,7 +6,8 @@ descriptor) live in awq_lanes.h / awq_quant.h, the host helpers of the entry poi
 awq_capi.hip (declared in awq_internal.h).  A private copy in a kernel file is how four
 spellings of one summation tree came about: a fix to one copy misses the others, and a selftest
 only proves the copy it compiles.  This test fails when a name of the list below is defined at
-namespace scope in more than one file, or not at all.
+namespace scope in more than one file, or not at all.  A second search keeps each kernel at one
+path: preprocessor conditionals may only test the AWQ_* names of CONDITIONAL_MACROS.
 """
 import glob
 import os
@@ -80,6 +81,29 @@ def test_helper_is_defined_in_one_file(name):
     found = {f: len(definitions(t, name)) for f, t in _sources().items()}
     found = {f: n for f, n in found.items() if n}
     assert list(found) == [HELPERS[name]], f"{name} is defined in {found}, expected only {HELPERS[name]}"
+
+
+# AWQ_* names a preprocessor conditional in csrc may test.  A compile-time A/B switch whose
+# default is the adopted path leaves a branch nobody builds in the middle of a kernel: once the
+# measurement is settled the switch goes, so a new one has to be added here on purpose.
+CONDITIONAL_MACROS = {
+    "AWQ_DIAG_H", "AWQ_LANES_H", "AWQ_QUANT_H",                     # header guards
+    "AWQ_DIAG", "AWQ_TRACE",                                        # the tool builds
+    # numeric tunables
+    "AWQ_WPB", "AWQ_SEARCH_MIN_WAVES", "AWQ_MIN_WAVES", "AWQ_MIN_WAVES_WIDE", "AWQ_LOAD_AUX", "AWQ_STORE_AUX",
+    "AWQ_SMALL_AUX", "AWQ_EXPORT_NT_MIN", "AWQ_RG_UNROLL",
+}
+
+
+def test_preprocessor_conditionals_test_only_listed_macros():
+    found = {}
+    for f, text in _sources().items():
+        for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b[^\n]*", text, re.M):
+            for name in re.findall(r"\bAWQ_\w+", line):
+                found.setdefault(name, set()).add(f)
+    assert {"AWQ_DIAG", "AWQ_TRACE"} <= set(found), "the search no longer sees the conditionals"
+    extra = {n: sorted(fs) for n, fs in found.items() if n not in CONDITIONAL_MACROS}
+    assert not extra, f"preprocessor conditionals test macros that are not on the allow-list: {extra}"
 
 
 def test_host_helpers_are_declared_once():
