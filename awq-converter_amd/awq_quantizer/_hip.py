@@ -140,6 +140,9 @@ SIGNATURES = {
     "awq_act_search_select": (_I32, [_P, _I32, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "awq_apply_input_scale": (_I32, [_P, _I32, _I64, _I64, _P, _P, _P]),
     "awq_fold_rows": (_I32, [_P, _I32, _I64, _I64, _P, _P, _P]),
+    "awq_act_stats_accum": (_I32, [_P, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "awq_rmsnorm_stats": (_I32, [_P, _I32, _I64, _I64, _P, ctypes.c_float, _P, _I64, _P, _P, _P, _P]),
+    "awq_swiglu_stats": (_I32, [_P, _P, _I32, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -493,6 +496,79 @@ def act_stats(x: torch.Tensor):
     check(load_library().awq_act_stats(ptr(x), AWQ_DTYPE[x.dtype], T, K, ptr(work), ptr(xm), ptr(xs), _stream(x)),
           "awq_act_stats")
     return xm, xs
+
+
+# ---- calibration pass (include/awq_hip.h awq_act_stats_accum / awq_rmsnorm_stats / awq_swiglu_stats) ----
+def _rows_view(t: torch.Tensor, what: str) -> int:
+    """Row stride (elements) of a 2-D view with unit column stride."""
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype not in (torch.bfloat16, torch.float16,
+                                                                             torch.float32):
+        raise ValueError(f"{what} takes a 2-D bf16 / fp16 / fp32 view with contiguous rows, got {tuple(t.shape)} "
+                         f"{t.dtype} strides {t.stride()}")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def calib_work_size(tokens: int, K: int, norm: bool = False) -> int:
+    """fp64 elements of the `work` argument (include/awq_hip.h)."""
+    return (-(-tokens // 2) if norm else 0) + 2 * (-(-tokens // ACT_ROW_BLOCK)) * K
+
+
+def _calib_work(work, tokens, K, device, norm=False):
+    n = calib_work_size(tokens, K, norm)
+    if work is None:
+        return torch.empty(max(n, 1), dtype=torch.float64, device=device)
+    if work.dtype != torch.float64 or work.numel() < n or not work.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous fp64 tensor of at least {n} elements")
+    return work
+
+
+def act_stats_accum(x: torch.Tensor, tokens_before: int, acc_abs: torch.Tensor, acc_sq: torch.Tensor,
+                    work: Optional[torch.Tensor] = None) -> None:
+    """Adds the rows of x [tokens, K] (any row stride) to the fp64 running sums (awq_act_stats_accum)."""
+    stride = _rows_view(x, "act_stats_accum")
+    T, K = x.shape
+    work = _calib_work(work, T, K, x.device)
+    check(load_library().awq_act_stats_accum(ptr(x), AWQ_DTYPE[x.dtype], T, K, stride, tokens_before, ptr(work),
+                                             ptr(acc_abs), ptr(acc_sq), _stream(x)), "awq_act_stats_accum")
+
+
+def rmsnorm_stats(x: torch.Tensor, weight: torch.Tensor, eps: float, tokens_before: int = 0,
+                  acc_abs: Optional[torch.Tensor] = None, acc_sq: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """transformers' LlamaRMSNorm of x [tokens, H] (awq_rmsnorm_stats); with accumulators, the
+    statistics of the result are added to them."""
+    if not x.is_contiguous() or x.dim() != 2 or weight.dtype != x.dtype or weight.numel() != x.shape[1]:
+        raise ValueError("rmsnorm_stats takes a contiguous [tokens, H] matrix and a weight [H] of its dtype")
+    T, H = x.shape
+    out = torch.empty_like(x) if out is None else out
+    work = _calib_work(work, T, H, x.device, norm=True)
+    check(load_library().awq_rmsnorm_stats(ptr(x), AWQ_DTYPE[x.dtype], T, H, ptr(weight.contiguous()), float(eps),
+                                           ptr(out), tokens_before, ptr(work), ptr(acc_abs), ptr(acc_sq), _stream(x)),
+          "awq_rmsnorm_stats")
+    return out
+
+
+def swiglu_stats(gate: torch.Tensor, up: torch.Tensor, tokens_before: int = 0,
+                 acc_abs: Optional[torch.Tensor] = None, acc_sq: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """silu(gate) * up with torch's roundings (awq_swiglu_stats); gate / up [tokens, K] share one row stride."""
+    sg, su = _rows_view(gate, "swiglu_stats"), _rows_view(up, "swiglu_stats")
+    if gate.shape != up.shape or gate.dtype != up.dtype or sg != su:
+        raise ValueError("swiglu_stats takes gate and up of one shape, dtype and row stride")
+    T, K = gate.shape
+    out = torch.empty((T, K), dtype=gate.dtype, device=gate.device) if out is None else out
+    work = _calib_work(work, T, K, gate.device) if acc_abs is not None else None
+    check(load_library().awq_swiglu_stats(ptr(gate), ptr(up), AWQ_DTYPE[gate.dtype], T, K, sg, ptr(out), tokens_before,
+                                          ptr(work), ptr(acc_abs), ptr(acc_sq), _stream(gate)), "awq_swiglu_stats")
+    return out
+
+
+def column_mean(acc: torch.Tensor, divisor: float) -> torch.Tensor:
+    """fp32(acc / divisor) of one fp64 [K] accumulator (awq_column_mean with one block)."""
+    out = torch.empty(acc.numel(), dtype=torch.float32, device=acc.device)
+    check(load_library().awq_column_mean(ptr(acc), 1, acc.numel(), float(divisor), ptr(out), _stream(acc)),
+          "awq_column_mean")
+    return out
 
 
 def weight_mean(weights, group_size: int) -> torch.Tensor:

@@ -74,6 +74,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="scale_method=awq: safetensors file of per-input-channel activation statistics, "
                         "'<weight name>.x_mean' (mean |x|) and '<weight name>.x_sq' (mean x^2), fp32 [in_features]; "
                         "weights without statistics are quantized RTN")
+    p.add_argument("--calib_ids", type=str, default=None,
+                   help="scale_method=awq: instead of --act_stats, token ids (safetensors with input_ids int64 "
+                        "[n, seq], or a .npy) to calibrate on first: the statistics come from a forward of the model "
+                        "on the GPU (awq_quantizer.calibrate; llama / mistral / qwen2)")
     p.add_argument("--no_duo_scaling", action="store_true",
                    help="scale_method=awq: channel scales x_mean^r instead of x_mean^r / w_mean^(1-r)")
     p.add_argument("--search_max_shrink", type=float, default=0.5,
@@ -854,6 +858,21 @@ def load_act_stats(path: str, logger=None) -> Dict[str, Tuple[torch.Tensor, torc
     return out
 
 
+def calibrate_for_main(args, device: str, logger) -> Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]:
+    """--calib_ids: the statistics load_act_stats would read, from a calibration forward on `device`
+    (awq_quantizer/calibration); None after logging why not."""
+    from .calibration import calibrate_model, read_input_ids
+    try:
+        ids = read_input_ids(args.calib_ids)
+        t0 = time.time()
+        stats = calibrate_model(args.model_id, ids, device=device, logger=logger)
+    except Exception as e:  # noqa: BLE001
+        logger.error(f"--calib_ids: calibration failed: {e}")
+        return None
+    logger.info(f"Calibrated {len(stats)} weights on {ids.numel()} tokens in {time.time() - t0:.2f} seconds")
+    return stats
+
+
 def _device_worker(*args, **kwargs) -> None:
     """Thread body of one device: a failure of the whole device (no GPU, no library) is
     logged; its tensors then count as not quantized."""
@@ -882,7 +901,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         logger = get_logger(name="awq_quantizer", level=args.log_level, to_file=args.log_file is not None,
                             file_path=args.log_file)
         os.makedirs(args.output_dir, exist_ok=True)
-        if args.fold_scales and (args.scale_method != "awq" or not args.act_stats
+        if args.calib_ids and args.act_stats:
+            logger.error("--calib_ids and --act_stats are mutually exclusive: the statistics come from one of them")
+            return 1
+        has_stats = bool(args.act_stats or args.calib_ids)
+        if args.fold_scales and (args.scale_method != "awq" or not has_stats
                                  or args.output_format != "autoawq"):
             logger.error("--fold_scales needs --scale_method awq, --act_stats and --output_format autoawq")
             return 1
@@ -954,7 +977,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                 return 1
         act_clip = None
         if args.act_clip:
-            if args.scale_method != "awq" or not args.act_stats:
+            if args.scale_method != "awq" or not has_stats:
                 logger.error("--act_clip needs --scale_method awq and --act_stats")
                 return 1
             if args.output_format != "packed" and not args.fold_scales:
@@ -965,16 +988,21 @@ def main(argv: Optional[List[str]] = None) -> int:
                 return 1
             act_clip = {"clip_grid": args.clip_grid, "clip_max_shrink": args.clip_max_shrink}
         act_stats = None
-        if args.act_stats:
+        if has_stats:
             if args.scale_method != "awq":
-                logger.error("--act_stats needs --scale_method awq")
+                logger.error(f"{'--calib_ids' if args.calib_ids else '--act_stats'} needs --scale_method awq")
                 return 1
             if autoawq and not args.fold_scales:
                 logger.error("--act_stats with --output_format autoawq: the searched input scales must be folded "
                              "into the ops producing each input first; use --output_format packed or reference "
                              "(results carry 'input_scale'), or add --fold_scales")
                 return 1
-            act_stats = load_act_stats(args.act_stats, logger)
+            if args.calib_ids:
+                act_stats = calibrate_for_main(args, devices[0], logger)
+                if act_stats is None:
+                    return 1
+            else:
+                act_stats = load_act_stats(args.act_stats, logger)
         elif args.scale_method == "awq":
             logger.warning("--scale_method awq without --act_stats: every weight is quantized RTN")
         if args.fold_scales:

@@ -640,6 +640,54 @@ int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, int64_t K, 
 int awq_fold_rows(const void* w, int dtype, int64_t rows, int64_t K, const float* row_scale, void* out,
                   void* stream);
 
+/* ---- Calibration pass (additive to ABI 17): the statistics awq_act_stats defines, taken while a
+ * model runs.  Every linear of a decoder block reads the output of a memory-bound op; these three
+ * entries produce that output where it is ours to produce (RMSNorm, the SwiGLU product) and add its
+ * column sums to fp64 running sums, micro-batch after micro-batch:
+ *   acc_abs[k] += sum_t |v[t,k]|,  acc_sq[k] += sum_t v[t,k]^2        (fp64 [K], caller-zeroed)
+ * in awq_act_stats' order continued across calls: t ascending inside 32-token sub-blocks, the
+ * sub-blocks ascending inside 256-token blocks, the blocks' sums added ascending onto the running
+ * value.  The caller guarantees that every call on an accumulator but the last has
+ * tokens % 256 == 0 and passes the number of tokens already added as tokens_before; a call with
+ * tokens_before % 256 != 0 is refused (AWQ_EINVAL, nothing launched).  After the last call
+ *   awq_column_mean(acc_abs, 1, K, T, x_mean),  awq_column_mean(acc_sq, 1, K, T, x_sq)
+ * (T = all tokens) give the bits of awq_act_stats on the concatenated rows.
+ * dtype D: bf16 / fp16 / fp32 (else AWQ_EUNSUPPORTED).  Checked in this order, nothing launched on
+ * a failure: the dtype; a negative tokens, K or tokens_before: AWQ_EINVAL; tokens == 0 or K == 0:
+ * AWQ_OK without a launch (the pointers are not looked at); tokens_before % 256; tokens > 65535 *
+ * 256 or K > 2^31: AWQ_EINVAL; row_stride < K; null pointers.  Caller-owned device memory, the
+ * caller's stream, no allocation, no synchronisation.
+ *
+ * awq_act_stats_accum: v = x [tokens, K] with a row stride in elements >= K (a column slice or
+ *   any other row-strided view).  work fp64 [2 * ceil(tokens / 256) * K].
+ * awq_rmsnorm_stats: transformers' LlamaRMSNorm with its roundings; x, out [tokens, H]
+ *   contiguous, weight [H] of dtype D, eps fp32:
+ *     v_t = sum_k RN_f32(x[t,k]^2) in fp32, in this order: the row is cut into 8-element chunks
+ *           c = 0 .. ceil(H/8)-1, each summed in order from +0; slot l (0..63) adds the sums of
+ *           chunks l, l + 64, l + 128, ... ascending from +0; v_t is the pairwise tree over the
+ *           64 slots, adjacent pairs first (awq_quantize_search's tree)
+ *     r_t = RN_f32(1 / RN_f32(sqrt(RN_f32(RN_f32(v_t / H) + eps))))   (IEEE / and sqrt)
+ *     out[t,k] = RN_D(weight[k] * RN_D(RN_f32(x[t,k] * r_t)))
+ *   and v = out.  acc_abs = acc_sq = NULL: the norm alone.  out may not alias x (x is read twice);
+ *   H <= 2^24.  work fp64 [ceil(tokens / 2) + 2 * ceil(tokens / 256) * H] (the first ceil(tokens/2)
+ *   hold r_t as fp32 and are all that the norm alone needs).
+ * awq_swiglu_stats: gate, up [tokens, K] with one row stride >= K (two column halves of a fused
+ *   [tokens, 2K] buffer), out [tokens, K] contiguous, overlapping neither input:
+ *     out = RN_D(RN_D(silu(g)) * u),  silu(g) = RN_f32(g / RN_f32(1 + expf(-g))) in fp32
+ *   and v = out.  expf is the device math library's (<= 1 ulp), not bit-reproducible elsewhere: out
+ *   is specified to 1 ulp of D (bf16 / fp16) of the fp64 expression, the sums exactly on the out
+ *   that was written.  g below -88.7 (expf overflows) gives -0 where the exact value is within
+ *   1e-36 of it.  acc_abs = acc_sq = NULL: the product alone (work is not looked at).
+ *   work fp64 [2 * ceil(tokens / 256) * K].
+ * Kernels, the same bits: K % 8 == 0, row strides % 8 == 0 and 16-B aligned pointers: 256-token x
+ * 32-column tiles with 16-B accesses; anything else: one lane per column and block. */
+int awq_act_stats_accum(const void* x, int dtype, int64_t tokens, int64_t K, int64_t row_stride,
+                        int64_t tokens_before, double* work, double* acc_abs, double* acc_sq, void* stream);
+int awq_rmsnorm_stats(const void* x, int dtype, int64_t tokens, int64_t H, const void* weight, float eps, void* out,
+                      int64_t tokens_before, double* work, double* acc_abs, double* acc_sq, void* stream);
+int awq_swiglu_stats(const void* gate, const void* up, int dtype, int64_t tokens, int64_t K, int64_t row_stride,
+                     void* out, int64_t tokens_before, double* work, double* acc_abs, double* acc_sq, void* stream);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
