@@ -1,0 +1,87 @@
+"""
+The CLI's --fold_scales run: one process, one GPU, the decoder blocks one by one.  main()
+imports this module only for such a run.
+"""
+
+import os
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import replace
+from typing import Dict, List
+
+import torch
+
+from .model_loading import TensorInfo
+from .output import _to_cpu, finish_run, model_type_of, save_autoawq
+from .pipeline import TIMINGS, StreamSettings, new_quantizer, quantize_stream_python
+
+
+def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo], ordered: List[TensorInfo],
+                      passthrough: List[TensorInfo], device: str, logger, start: float) -> int:
+    """--fold_scales: the decoder blocks one by one (quantization/block_plan.py) — a block's members
+    and producers read together (the next block read ahead on the reader pool), then
+    AWQQuantizer.quantize_block, export_autoawq per result and D2H; linears in no group take the
+    regular path (RTN).  A block that fails is copied unquantized (modules_to_not_convert) with its
+    norms and biases left unfolded.  Writes model.safetensors (folded norm weights and biases in
+    place of the source's), the configs, and awq_scales.safetensors: every block's "scales"."""
+    from safetensors.torch import save_file
+    from .quantization.block_plan import plan_blocks
+    by_name = {i.name: i for i in index}
+    plan = plan_blocks({i.name: i.shape for i in index}, model_type_of(loader), args.group_size)
+    linear = {i.name for i in ordered}
+    quantizer = new_quantizer(args, device)
+    try:
+        quantizer.compute_device()
+    except Exception as e:  # noqa: BLE001
+        logger.error(f"Quantization on {device} failed: {e}")
+        return 1
+    clip_kw = {"clip": True, **cfg.act_clip} if cfg.act_clip else {}
+    results: Dict[str, Dict[str, torch.Tensor]] = {}
+    overrides: Dict[str, torch.Tensor] = {}
+    sidecar: Dict[str, torch.Tensor] = {}
+    blocks = [b for b in plan if all(m in linear for m in b.members())]
+    grouped = {m for b in blocks for m in b.members()}
+    rest = [i for i in ordered if i.name not in grouped]
+    logger.info(f"Scale folding: {len(blocks)} decoder blocks, {len(grouped)} linears in layer groups, "
+                f"{len(rest)} in none (RTN)")
+    inside = [i.name for i in rest if any(i.name.startswith(b.prefix + ".") for b in plan)]
+    if inside:   # none in llama / mistral / qwen2; one reading a folded norm's output would see x / s unscaled
+        logger.warning(f"linears inside a decoder block that belong to no layer group are quantized without an "
+                       f"input scale; if one reads a folded norm's output the checkpoint is wrong: {inside}")
+    with ThreadPoolExecutor(max_workers=max(1, args.num_workers)) as pool:
+        futs = {}
+
+        def submit(k):
+            if k < len(blocks) and k not in futs:
+                futs[k] = {n: pool.submit(loader.read, by_name[n]) for n in blocks[k].tensor_names()}
+
+        submit(0)
+        for k, block in enumerate(blocks):
+            submit(k + 1)
+            try:
+                tensors = {n: f.result() for n, f in futs.pop(k).items()}
+                out = quantizer.quantize_block(tensors, cfg.act_stats, block, **clip_kw)
+                exported = {n: _to_cpu(quantizer.export_autoawq(r)) for n, r in out["results"].items()}
+                host_folded = _to_cpu(out["folded"])
+                host_scales = _to_cpu(out["scales"])
+            except Exception as e:  # noqa: BLE001  (the block's linears are copied unquantized)
+                logger.error(f"Error quantizing block {block.prefix}: {e}")
+                continue
+            results.update(exported)
+            overrides.update(host_folded)
+            sidecar.update(host_scales)
+            logger.info(f"Successfully quantized block: {block.prefix} on {device} (folded groups: "
+                        f"{[n for n, g in out['groups'].items() if g['folded']]})")
+    if rest:   # the regular pipeline, RTN: no statistics, no clip search
+        quantize_stream_python(replace(cfg, act_stats=None, act_clip=None), loader, rest, quantizer, device,
+                               results, threading.Lock(), logger)
+    TIMINGS["quantize_s"] = time.time() - start
+    quantized = {i.name: results[i.name] for i in ordered if i.name in results}
+
+    def save():
+        save_autoawq(quantized, loader, passthrough, args.output_dir, args, logger,
+                     failed=[i for i in ordered if i.name not in quantized], overrides=overrides)
+        save_file({k: v.contiguous() for k, v in sidecar.items()},
+                  os.path.join(args.output_dir, "awq_scales.safetensors"), metadata={"format": "pt"})
+    return finish_run(args, ordered, quantized, logger, start, save)

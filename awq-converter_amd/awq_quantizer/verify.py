@@ -417,7 +417,7 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
                         f"snr {e['snr_db']:.2f} dB  nonfinite {e['nonfinite']}")
         judged = set()
         if has_sidecar:
-            from .main import model_type_of
+            from .output import model_type_of
             shapes = {n: tuple(i.shape) for n, i in index.items()}
             for name, why in fold_audit(shapes, model_type_of(loader), cfg["group_size"], sidecar,
                                         lambda n: loader.read(index[n]), read_ckpt, fold_fn).items():

@@ -155,7 +155,7 @@ def test_cpu_share_reads_cgroup_quota(monkeypatch, tmp_path):
     """cpu_share: the affinity set, capped by a cgroup v2 quota (the GPU box: cpu.max 1600000
     100000 = 16 CPUs while os.cpu_count() shows the node's 256)."""
     import builtins
-    from awq_quantizer import main as m
+    from awq_quantizer import output as m
     real_open = builtins.open
     monkeypatch.setattr(m.os, "sched_getaffinity", lambda pid: set(range(256)), raising=False)
 
@@ -177,7 +177,7 @@ def test_cpu_share_reads_cgroup_quota(monkeypatch, tmp_path):
 def test_writer_threads_by_output_size(monkeypatch):
     """Chunk-writer pool sized by output bytes: 2-4 writers below ~2 GB of output (more
     stalled the pipeline's HIP calls), up to 8 above; STREAM_OPTS["writers"] overrides."""
-    from awq_quantizer import main as m
+    from awq_quantizer import output as m
     from awq_quantizer.model_loading.safetensors_loader import TensorInfo
     monkeypatch.setattr(m, "cpu_share", lambda: 16)
 
@@ -197,7 +197,7 @@ def test_chunk_writer_widens_pool_at_close(tmp_path, monkeypatch):
     reported (or at close()) the rest of the pool drains the backlog (same files either way)."""
     import threading
     import time as _t
-    from awq_quantizer import main as m
+    from awq_quantizer import output as m
     monkeypatch.setattr(m, "cpu_share", lambda: 16)          # tail pool: 8
     active, peak, lock = [0], [0], threading.Lock()
     real = m._write_chunk
@@ -873,11 +873,11 @@ def test_native_stream_failed_chunk_write_does_not_hang(tmp_path, monkeypatch):
     chunk's range is released, the producer stops at its next result, and main() returns
     non-zero — within seconds."""
     import threading as th
-    from awq_quantizer import main as M
+    from awq_quantizer import main as M, output as O
     d = _model_dir(tmp_path, _ring_model(), files=3)
     for k, v in (("slot_bytes", 64 << 10), ("host_ring_bytes", 64 << 10), ("dev_ring_bytes", 64 << 10)):
         monkeypatch.setitem(M.STREAM_OPTS, k, v)
-    real = M._write_chunk
+    real = O._write_chunk
     calls = []
 
     def failing(chunk, output_dir, c, *a, **kw):
@@ -886,7 +886,7 @@ def test_native_stream_failed_chunk_write_does_not_hang(tmp_path, monkeypatch):
             raise OSError(28, "No space left on device (injected)")
         return real(chunk, output_dir, c, *a, **kw)
 
-    monkeypatch.setattr(M, "_write_chunk", failing)
+    monkeypatch.setattr(O, "_write_chunk", failing)
     rc = []
     t = th.Thread(target=lambda: rc.append(M.main(["--model_id", d, "--output_dir", str(tmp_path / "out"),
                                                   "--log_level", "CRITICAL", "--chunk_size", "3",

@@ -42,8 +42,9 @@ def test_product_library_has_no_diagnostics_entry_points():
     assert not hasattr(lib, "awq_set_tuning")
     if os.path.exists(_hip.DIAG_LIB_PATH):
         assert hasattr(_hip.load_diag_library(), "awq_set_tuning")
-    src = open(os.path.join(ROOT, "awq-converter_amd", "awq_quantizer", "main.py")).read()
-    assert "os.environ" not in src.replace('os.environ.get("AWQ_DIST_BACKEND"', "")
+    for mod in ("main", "options", "output", "pipeline", "fold_cli", "dist_cli"):     # the CLI's modules
+        src = open(os.path.join(ROOT, "awq-converter_amd", "awq_quantizer", mod + ".py")).read()
+        assert "os.environ" not in src.replace('os.environ.get("AWQ_DIST_BACKEND"', ""), mod
 
 
 def test_diag_tuning_rejects_a_retired_fp64_span():

@@ -4,7 +4,7 @@ the AutoAWQ shards, and the failure agreement (a rank that fails as a whole make
 rank exit 1 instead of leaving the others blocked in a collective).
 
 The quantize pipeline itself needs the GPU, so the workers replace
-`awq_quantizer.main.quantize_stream` with a fake that returns deterministic result dicts
+`awq_quantizer.pipeline.quantize_stream` with a fake that returns deterministic result dicts
 (same contract: results into `out`, every tensor reported to `on_done`); everything after
 it — chunk numbering, renames, metadata.json, shard index, agreement — is the product
 code.  Bar: the union of the per-rank files, loaded through metadata.json (or the shard
@@ -62,9 +62,7 @@ def fake_result(name, fmt, shape=(3, 16)):
 
 
 def _fake_stream(fmt, fail_rank, rank):
-    def quantize_stream(loader, infos, quantizer, device, readers, lookahead, packed, out, lock, logger,
-                        memory_efficient=False, keep_on_device=False, batch_bytes=0, export_autoawq=False,
-                        act_stats=None, on_done=None, **_):
+    def quantize_stream(cfg, loader, infos, quantizer, device, out, lock, logger, on_done=None, **_):
         for k, info in enumerate(infos):
             if rank == fail_rank and k == 1:
                 raise RuntimeError("device lost (injected)")
@@ -72,7 +70,7 @@ def _fake_stream(fmt, fail_rank, rank):
                 if on_done:
                     on_done(info.name, None)
                 continue
-            r = fake_result(info.name, "autoawq" if export_autoawq else fmt, tuple(info.shape))
+            r = fake_result(info.name, "autoawq" if cfg.export_autoawq else fmt, tuple(info.shape))
             with lock:
                 out.update({info.name: r})
             if on_done:
@@ -86,12 +84,12 @@ def _worker(rank, world, port, model_dir, out_dir, fmt, extra, fail_rank, q, inj
     if isinstance(out_dir, list):      # per-rank directories: not one shared output directory
         out_dir = out_dir[rank]
     try:
-        from awq_quantizer import main as M
-        M.quantize_stream = _fake_stream(fmt, fail_rank, rank)
+        from awq_quantizer import dist_cli, main as M, pipeline
+        pipeline.quantize_stream = _fake_stream(fmt, fail_rank, rank)
         if inject == "meta" and rank == 0:          # the last commit step fails after the renames
             def bad_meta(*a, **k):
                 raise OSError("disk full (injected)")
-            M._write_metadata = bad_meta
+            dist_cli._write_metadata = bad_meta
         rc = M.main(["--model_id", model_dir, "--output_dir", out_dir, "--log_level", "CRITICAL", "--chunk_size", "4",
                      "--output_format", "packed" if fmt == "sized" else fmt] + extra)
         q.put((rank, rc))
@@ -208,14 +206,14 @@ def test_autoawq_shards_and_failed_linears(tmp_path, world):
         json.dump({"model_type": "llama"}, f)
     out = str(tmp_path / "out")
     if world == 1:
-        from awq_quantizer import main as M
-        saved = M.quantize_stream
-        M.quantize_stream = _fake_stream("autoawq", -1, 0)
+        from awq_quantizer import main as M, pipeline
+        saved = pipeline.quantize_stream
+        pipeline.quantize_stream = _fake_stream("autoawq", -1, 0)
         try:
             assert M.main(["--model_id", model_dir, "--output_dir", out, "--log_level", "CRITICAL",
                            "--output_format", "autoawq"]) == 0
         finally:
-            M.quantize_stream = saved
+            pipeline.quantize_stream = saved
         got = load_file(os.path.join(out, "model.safetensors"))
     else:
         assert _run(world, model_dir, out, "autoawq") == [0] * world
