@@ -116,6 +116,9 @@ SIGNATURES = {
     "awq_selftest": (_I32, [_I32, _P, _P]),
     "awq_quant_error_work_bytes": (_I64, [_I64, _I64, _I64]),
     "awq_quant_error": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "awq_output_error_work_bytes": (_I64, [_I64, _I64]),
+    "awq_output_error": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P,
+                                _P]),
     "awq_stream_table_bytes": (_I64, [_I64]),
     "awq_stream_start": (_I32, [ctypes.POINTER(StreamItem), _I32, ctypes.POINTER(StreamConfig),
                                 ctypes.POINTER(ctypes.c_void_p)]),
@@ -468,6 +471,43 @@ def quant_error(w: torch.Tensor, rows: int, K: int, L: int, bits: int, symmetric
                               ptr(qzeros), ptr(scales), ptr(stats), ptr(bad), ptr(work), ptr(tot), _stream(w)),
           "awq_quant_error")
     return stats, bad, tot
+
+
+def output_error(w: torch.Tensor, L: int, bits: int, symmetric: bool, qweight, qzeros, scales, x: torch.Tensor,
+                 col_scale: Optional[torch.Tensor] = None, *, ref: bool = True, err: bool = False,
+                 err_sq: Optional[torch.Tensor] = None):
+    """awq_output_error: what the packed result costs at the linear's output on the samples x.
+    w [N, K] (device, contiguous), x [T, K] of w's dtype (device, unit column stride: a row-strided
+    view is taken as it is), col_scale fp32 [K] or None.  -> (err_sq fp32 [N], ref_sq fp32 [N] or
+    None, err fp32 [N, T] or None) on w's device.  err_sq: a caller's fp32 [N] view to write into
+    (the scale search's part rows).  Allocates the workspace."""
+    if w.dtype not in AWQ_DTYPE:
+        raise RuntimeError(f"awq_output_error: unsupported weight dtype {w.dtype}")
+    if w.dim() != 2 or not w.is_contiguous():
+        raise ValueError("awq_output_error takes a contiguous 2-D weight")
+    N, K = w.shape
+    if x.dim() != 2 or x.shape[1] != K or x.dtype != w.dtype or x.device != w.device or (K > 1 and x.stride(1) != 1):
+        raise ValueError(f"awq_output_error: samples must be [tokens, {K}] {w.dtype} on {w.device} with contiguous "
+                         f"rows, got {tuple(x.shape)} {x.dtype} strides {x.stride()}")
+    T = x.shape[0]
+    xs = x.stride(0) if T > 1 else max(x.stride(0), K)
+    if col_scale is not None and (col_scale.dtype != torch.float32 or col_scale.numel() != K
+                                  or col_scale.device != w.device or not col_scale.is_contiguous()):
+        raise ValueError(f"awq_output_error: col_scale must be a contiguous fp32 [{K}] on {w.device}")
+    lib = load_library()
+    dev = w.device
+    if err_sq is None:
+        err_sq = torch.zeros(N, dtype=torch.float32, device=dev)
+    elif err_sq.dtype != torch.float32 or err_sq.numel() != N or err_sq.device != dev or not err_sq.is_contiguous():
+        raise ValueError(f"awq_output_error: err_sq must be a contiguous fp32 [{N}] on {dev}")
+    # (zeros: an empty N, K or T writes nothing, and the sums over nothing are 0)
+    ref_sq = torch.zeros(N, dtype=torch.float32, device=dev) if ref else None
+    e = torch.zeros((N, T), dtype=torch.float32, device=dev) if err else None
+    work = torch.empty(max(1, lib.awq_output_error_work_bytes(N, T) // 4), dtype=torch.float32, device=dev)
+    check(lib.awq_output_error(ptr(w), AWQ_DTYPE[w.dtype], N, K, L, bits, int(bool(symmetric)), ptr(qweight),
+                               ptr(qzeros), ptr(scales), ptr(col_scale), ptr(x), T, xs, ptr(work), ptr(err_sq),
+                               ptr(ref_sq), ptr(e), _stream(w)), "awq_output_error")
+    return err_sq, ref_sq, e
 
 
 def selftest(which: int, device: torch.device) -> int:

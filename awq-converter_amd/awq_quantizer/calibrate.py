@@ -6,6 +6,9 @@ directory and token ids, on the GPU (awq_quantizer/calibration).
          --n_samples 128 --seq_len 512
 
 --input_ids: a safetensors file with `input_ids` int64 [n, seq], or a .npy of the same.
+--samples_output FILE [--n_sample_tokens 512]: also keeps evenly spread token rows of every linear's
+input, written to a second safetensors file (the statistics file is unchanged) for the output-space
+loss and report (main --act_samples, verify --act_samples).
 --text_file: needs the `tokenizers` package and DIR/tokenizer.json; the text is tokenised,
 concatenated and cut into seq_len blocks, the first n_samples kept.
 Every argument error exits 1 before any device work.
@@ -34,6 +37,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--compute_dtype", type=str, default=None, choices=["bfloat16", "float16", "float32"],
                    help="Dtype of the forward (default: the checkpoint's)")
     p.add_argument("--batch_tokens", type=int, default=8192, help="Tokens per micro-batch (whole sequences)")
+    p.add_argument("--samples_output", type=str, default=None,
+                   help="Also write token samples of every linear's input ('<block>.<group>.samples', a second "
+                        "safetensors file) for the output-space loss (--act_samples)")
+    p.add_argument("--n_sample_tokens", type=int, default=512, help="--samples_output: token rows kept per input")
     p.add_argument("--device", type=str, default="cuda", help="The GPU to run on (there is no CPU path)")
     p.add_argument("--log_level", type=str, default="INFO", choices=["DEBUG", "INFO", "WARNING", "ERROR", "CRITICAL"])
     return p
@@ -73,6 +80,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         from .calibration import parse_config, read_config
         if args.batch_tokens <= 0:
             raise ValueError("--batch_tokens must be positive")
+        if args.samples_output and args.n_sample_tokens <= 0:
+            raise ValueError("--n_sample_tokens must be positive")
         if not os.path.isdir(args.model_id):
             raise ValueError(f"--model_id: {args.model_id} is not a directory")
         cfg = read_config(args.model_id)
@@ -82,12 +91,17 @@ def main(argv: Optional[List[str]] = None) -> int:
         logger.error(str(e))
         return 1
     try:
-        from .calibration import calibrate_model, save_act_stats
+        from .calibration import calibrate_model, save_act_samples, save_act_stats
         t0 = time.time()
+        samples = {} if args.samples_output else None
         stats = calibrate_model(args.model_id, ids, compute_dtype=args.compute_dtype, batch_tokens=args.batch_tokens,
-                                device=args.device, logger=logger)
+                                device=args.device, logger=logger,
+                                n_sample_tokens=args.n_sample_tokens if args.samples_output else 0, samples_out=samples)
         seconds = time.time() - t0
         save_act_stats(stats, args.output)
+        if args.samples_output:
+            save_act_samples(samples, args.samples_output)
+            logger.info(f"Wrote token samples of {len(samples)} inputs to {args.samples_output}")
     except Exception as e:  # noqa: BLE001
         logger.error(f"Calibration failed: {e}")
         return 1

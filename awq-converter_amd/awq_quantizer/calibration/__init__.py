@@ -14,13 +14,13 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .forward import (CalibrationConfigError, DecoderConfig, HipOps, parse_config, plan_micro_batches, read_config,
-                      rope_inv_freq, run_decoder)
+from .forward import (BLOCK_LINEARS, CalibrationConfigError, DecoderConfig, HipOps, parse_config, plan_micro_batches,
+                      read_config, rope_inv_freq, run_decoder, sample_rows)
 from .stats import StatsAccumulator
 
 __all__ = ["StatsAccumulator", "CalibrationConfigError", "DecoderConfig", "HipOps", "calibrate_model", "chunk_text",
            "parse_config", "plan_micro_batches", "read_config", "read_input_ids", "rope_inv_freq", "run_decoder",
-           "save_act_stats"]
+           "save_act_stats", "sample_rows", "save_act_samples", "load_act_samples"]
 
 _DTYPES = {"bfloat16": torch.bfloat16, "float16": torch.float16, "float32": torch.float32,
            "float64": torch.float64}
@@ -72,10 +72,13 @@ def resolve_dtype(compute_dtype, checkpoint_dtype: Optional[torch.dtype]) -> tor
 
 
 def calibrate_model(model_dir: str, input_ids, compute_dtype=None, batch_tokens: int = 8192, device="cuda",
-                    ops=None, logger=None) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+                    ops=None, logger=None, n_sample_tokens: int = 0,
+                    samples_out: Optional[Dict[str, torch.Tensor]] = None
+                    ) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
     """Statistics of every linear's input over input_ids [n, seq]: weight name -> (x_mean, x_sq), fp32
     [in_features] on the CPU.  compute_dtype: the checkpoint's dtype by default; float32 is allowed
-    (float64 only with injected ops: the kernels take bf16 / fp16 / fp32)."""
+    (float64 only with injected ops: the kernels take bf16 / fp16 / fp32).  n_sample_tokens > 0
+    with a dict samples_out: run_decoder's token samples, "<block>.<group>.samples" -> [n, in]."""
     from ..model_loading.safetensors_loader import SafetensorsLoader
     ids = check_input_ids(input_ids)
     if batch_tokens <= 0:
@@ -91,7 +94,8 @@ def calibrate_model(model_dir: str, input_ids, compute_dtype=None, batch_tokens:
         dtype = resolve_dtype(compute_dtype, embed.dtype if embed is not None else None)
         if isinstance(ops, HipOps) and dtype == torch.float64:
             raise ValueError("compute_dtype float64: the calibration kernels take bfloat16 / float16 / float32")
-        return run_decoder(loader, cfg, ids, dtype, device, ops, batch_tokens=batch_tokens, logger=logger)
+        return run_decoder(loader, cfg, ids, dtype, device, ops, batch_tokens=batch_tokens, logger=logger,
+                           n_sample_tokens=n_sample_tokens, samples_out=samples_out)
     finally:
         loader.close()
 
@@ -104,3 +108,32 @@ def save_act_stats(stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]], path: st
         flat[name + ".x_sq"] = s.detach().float().cpu().contiguous().clone()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     save_file(flat, path, metadata={"format": "pt"})
+
+
+def save_act_samples(samples: Dict[str, torch.Tensor], path: str) -> None:
+    """The token samples of a calibration pass ("<block>.<group>.samples" -> [tokens, in]) as their
+    own safetensors file: the statistics file keeps exactly its keys."""
+    from safetensors.torch import save_file
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    save_file({k: v.detach().cpu().contiguous().clone() for k, v in samples.items()}, path, metadata={"format": "pt"})
+
+
+def group_samples(flat: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """"<block>.<group>.samples" tensors -> weight name -> its group's tensor (BLOCK_LINEARS)."""
+    out = {}
+    for key, t in flat.items():
+        if not key.endswith(".samples"):
+            continue
+        block, _, group = key[: -len(".samples")].rpartition(".")
+        for name, mods in BLOCK_LINEARS:
+            if name == group:
+                for m in mods:
+                    out[f"{block}.{m}.weight"] = t
+    return out
+
+
+def load_act_samples(path: str) -> Dict[str, torch.Tensor]:
+    """A --samples_output file -> weight name -> token samples [tokens, in_features] of its input
+    (the members of a group share one tensor)."""
+    from safetensors.torch import load_file
+    return group_samples(load_file(path))

@@ -204,6 +204,13 @@ def plan_micro_batches(n: int, seq: int, batch_tokens: int) -> Tuple[List[Tuple[
     return spans, fused
 
 
+def sample_rows(total: int, n: int) -> List[int]:
+    """The token rows kept as samples: t_j = floor(j * total / n) for j < n — evenly spread over the
+    token-major activation, ascending, distinct (n is cut to total); n <= 0 keeps nothing."""
+    n = min(int(n), int(total))
+    return [j * total // n for j in range(n)] if n > 0 else []
+
+
 def _linear_names(prefix: str, names) -> Dict[str, List[str]]:
     out = {}
     for group, mods in BLOCK_LINEARS:
@@ -212,8 +219,13 @@ def _linear_names(prefix: str, names) -> Dict[str, List[str]]:
 
 
 def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torch.dtype, device, ops,
-                batch_tokens: int = 8192, readers: int = 4, logger=None) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
-    """The block-by-block pass.  Returns weight name -> (x_mean, x_sq) (fp32, on the CPU)."""
+                batch_tokens: int = 8192, readers: int = 4, logger=None, n_sample_tokens: int = 0,
+                samples_out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+    """The block-by-block pass.  Returns weight name -> (x_mean, x_sq) (fp32, on the CPU).
+    n_sample_tokens > 0 also keeps, per block and distinct input, the rows sample_rows(n * seq,
+    n_sample_tokens) of the token-major activation (the tensors the producers return, compute
+    dtype, gathered per micro-batch) in samples_out["<block prefix>.<group>.samples"] (CPU);
+    0 keeps nothing and changes nothing."""
     device = torch.device(device)
     index = {i.name: i for i in loader.tensor_index()}
     root = "model." if "model.embed_tokens.weight" in index else ""
@@ -237,6 +249,8 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
         return t.to(device=device, dtype=dtype, non_blocking=True)
 
     results: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+    keep = torch.tensor(sample_rows(n * seq, n_sample_tokens if samples_out is not None else 0), dtype=torch.int64,
+                        device=device)
 
     def publish(acc, names):
         if names:
@@ -270,10 +284,18 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
             inter = w["mlp.gate_proj.weight"].shape[0]
             accs = {"attn_in": ops.new_acc(H), "attn_out": ops.new_acc(w["self_attn.o_proj.weight"].shape[1]),
                     "mlp_in": ops.new_acc(H), "mlp_out": ops.new_acc(inter)}
+            kept = {g: [] for g in accs}
             for a, b in spans:
                 x = hidden[a * seq:b * seq]                       # [T, H] view of the resident states
                 m = b - a
+                sel = keep[(keep >= a * seq) & (keep < b * seq)] - a * seq if keep.numel() else None
+
+                def take(group, t):
+                    if sel is not None and sel.numel():
+                        kept[group].append(t.index_select(0, sel))
+
                 hn = ops.rmsnorm(x, w["input_layernorm.weight"], cfg.eps, accs["attn_in"], fused)
+                take("attn_in", hn)
                 qkv = F.linear(hn, w_qkv, b_qkv).view(m, seq, nh + 2 * nkv, hd).transpose(1, 2)
                 q, k, v = qkv[:, :nh], qkv[:, nh:nh + nkv], qkv[:, nh + nkv:]
                 q = q * cos + rotate_half(q) * sin
@@ -284,13 +306,18 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
                 att = F.scaled_dot_product_attention(q, k, v, is_causal=True)
                 att = att.transpose(1, 2).reshape(m * seq, nh * hd)
                 ops.accum(att, accs["attn_out"])
+                take("attn_out", att)
                 x += F.linear(att, w["self_attn.o_proj.weight"], w.get("self_attn.o_proj.bias"))
                 hn = ops.rmsnorm(x, w["post_attention_layernorm.weight"], cfg.eps, accs["mlp_in"], fused)
+                take("mlp_in", hn)
                 gu = F.linear(hn, w_gu, b_gu)                     # [T, 2 * inter]: gate | up
                 act = ops.swiglu(gu[:, :inter], gu[:, inter:], accs["mlp_out"], fused)
+                take("mlp_out", act)
                 x += F.linear(act, w["mlp.down_proj.weight"], w.get("mlp.down_proj.bias"))
             for group, acc in accs.items():
                 publish(acc, lin[group])
+                if kept[group]:
+                    samples_out[f"{p}.{group}.samples"] = torch.cat(kept[group]).cpu()
             if logger:
                 logger.info(f"Calibrated block: {p}")
         if "lm_head.weight" in index:

@@ -18,13 +18,16 @@ from .pipeline import TIMINGS, StreamSettings, new_quantizer, quantize_stream_py
 
 
 def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo], ordered: List[TensorInfo],
-                      passthrough: List[TensorInfo], device: str, logger, start: float) -> int:
+                      passthrough: List[TensorInfo], device: str, logger, start: float,
+                      act_samples: Dict[str, torch.Tensor] = None) -> int:
     """--fold_scales: the decoder blocks one by one (quantization/block_plan.py) — a block's members
     and producers read together (the next block read ahead on the reader pool), then
     AWQQuantizer.quantize_block, export_autoawq per result and D2H; linears in no group take the
     regular path (RTN).  A block that fails is copied unquantized (modules_to_not_convert) with its
     norms and biases left unfolded.  Writes model.safetensors (folded norm weights and biases in
-    place of the source's), the configs, and awq_scales.safetensors: every block's "scales"."""
+    place of the source's), the configs, and awq_scales.safetensors: every block's "scales".
+    act_samples (--search_loss output): "<block prefix>.<group>.samples" -> token samples; each
+    block's four tensors go to quantize_block with loss="output"."""
     from safetensors.torch import save_file
     from .quantization.block_plan import plan_blocks
     by_name = {i.name: i for i in index}
@@ -37,6 +40,7 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
         logger.error(f"Quantization on {device} failed: {e}")
         return 1
     clip_kw = {"clip": True, **cfg.act_clip} if cfg.act_clip else {}
+    output_loss = act_samples is not None
     results: Dict[str, Dict[str, torch.Tensor]] = {}
     overrides: Dict[str, torch.Tensor] = {}
     sidecar: Dict[str, torch.Tensor] = {}
@@ -61,7 +65,12 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
             submit(k + 1)
             try:
                 tensors = {n: f.result() for n, f in futs.pop(k).items()}
-                out = quantizer.quantize_block(tensors, cfg.act_stats, block, **clip_kw)
+                loss_kw = {}
+                if output_loss:
+                    smp = {g: act_samples[f"{block.prefix}.{g}.samples"] for g in block.groups
+                           if f"{block.prefix}.{g}.samples" in act_samples}
+                    loss_kw = {"loss": "output", "samples": smp}
+                out = quantizer.quantize_block(tensors, cfg.act_stats, block, **clip_kw, **loss_kw)
                 exported = {n: _to_cpu(quantizer.export_autoawq(r)) for n, r in out["results"].items()}
                 host_folded = _to_cpu(out["folded"])
                 host_scales = _to_cpu(out["scales"])
@@ -73,6 +82,10 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
             sidecar.update(host_scales)
             logger.info(f"Successfully quantized block: {block.prefix} on {device} (folded groups: "
                         f"{[n for n, g in out['groups'].items() if g['folded']]})")
+            for gname, g in out["groups"].items():
+                if g.get("loss"):
+                    logger.info(f"{block.prefix}.{gname}: search loss {g['loss']}, winner {g['best']}/"
+                                f"{args.search_grid} (diagonal loss: {g['diag_best']}/{args.search_grid})")
     if rest:   # the regular pipeline, RTN: no statistics, no clip search
         quantize_stream_python(replace(cfg, act_stats=None, act_clip=None), loader, rest, quantizer, device,
                                results, threading.Lock(), logger)

@@ -167,14 +167,18 @@ def load_act_stats(path: str, logger=None) -> Dict[str, Tuple[torch.Tensor, torc
     return out
 
 
-def calibrate_for_main(args, device: str, logger) -> Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]:
+def calibrate_for_main(args, device: str, logger,
+                       samples_out: Optional[Dict[str, torch.Tensor]] = None
+                       ) -> Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]:
     """--calib_ids: the statistics load_act_stats would read, from a calibration forward on `device`
-    (awq_quantizer/calibration); None after logging why not."""
+    (awq_quantizer/calibration); None after logging why not.  samples_out (--search_loss output):
+    a dict the forward fills with --n_sample_tokens token samples per linear input."""
     from .calibration import calibrate_model, read_input_ids
     try:
         ids = read_input_ids(args.calib_ids)
         t0 = time.time()
-        stats = calibrate_model(args.model_id, ids, device=device, logger=logger)
+        stats = calibrate_model(args.model_id, ids, device=device, logger=logger, samples_out=samples_out,
+                                n_sample_tokens=args.n_sample_tokens if samples_out is not None else 0)
     except Exception as e:  # noqa: BLE001
         logger.error(f"--calib_ids: calibration failed: {e}")
         return None
@@ -283,6 +287,10 @@ def main(argv: Optional[List[str]] = None) -> int:
             logger.error(err)
             return 1
 
+        if args.act_samples and not os.path.isfile(args.act_samples):   # before the model is read
+            logger.error(f"--act_samples: {args.act_samples} does not exist")
+            return 1
+
         devices = _pick_devices(args, logger)
         from . import distributed as D
         world = D.env_world()[2]
@@ -313,8 +321,16 @@ def main(argv: Optional[List[str]] = None) -> int:
             return 1
 
         act_stats = None
+        act_samples = None      # --search_loss output: "<block>.<group>.samples" -> [tokens, in]
+        if args.search_loss == "output":
+            act_samples = {}
+            if args.act_samples:
+                from safetensors.torch import load_file
+                act_samples = load_file(args.act_samples)
+                logger.info(f"Loaded token samples of {len(act_samples)} inputs from {args.act_samples}")
         if args.calib_ids:
-            act_stats = calibrate_for_main(args, devices[0], logger)
+            act_stats = calibrate_for_main(args, devices[0], logger,
+                                           samples_out=act_samples if args.search_loss == "output" else None)
             if act_stats is None:
                 return 1
         elif args.act_stats:
@@ -326,7 +342,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                                        export_autoawq=autoawq, act_stats=act_stats, act_clip=act_clip_of(args))
         if args.fold_scales:
             from .fold_cli import _main_fold_scales
-            return _main_fold_scales(args, cfg, loader, index, ordered, passthrough, devices[0], logger, start)
+            return _main_fold_scales(args, cfg, loader, index, ordered, passthrough, devices[0], logger, start,
+                                     act_samples=act_samples)
         if world > 1:   # torchrun: one process per GPU, LPT shard, RCCL gather to rank 0
             from .dist_cli import _main_distributed
             return _main_distributed(args, cfg, loader, ordered, logger, start, passthrough)

@@ -43,6 +43,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "layer group of every decoder block (q/k/v, o, gate/up, down), fold 1/s into the op producing "
                         "that input (norm weight, v_proj / up_proj rows) and write a loadable activation-aware "
                         "AutoAWQ checkpoint plus awq_scales.safetensors (llama / mistral / qwen2 tensor names)")
+    p.add_argument("--search_loss", type=str, default="diag", choices=["diag", "output"],
+                   help="--fold_scales: how the scale search scores a candidate. diag: the diagonal loss from the "
+                        "statistics; output: the layer group's output error on token samples (--act_samples, or "
+                        "collected by the --calib_ids forward)")
+    p.add_argument("--act_samples", type=str, default=None,
+                   help="--search_loss output: token samples written by awq_quantizer.calibrate --samples_output")
+    p.add_argument("--n_sample_tokens", type=int, default=512,
+                   help="--search_loss output with --calib_ids: token rows kept per linear input")
     p.add_argument("--clip_grid", type=int, default=20, help="--act_clip: grid size of the range shrinks")
     p.add_argument("--clip_max_shrink", type=float, default=0.5,
                    help="--act_clip: largest shrink of the group range tried")
@@ -106,6 +114,18 @@ def check_flags(args) -> Optional[str]:
     if args.fold_scales and (args.scale_method != "awq" or not has_stats(args)
                              or args.output_format != "autoawq"):
         return "--fold_scales needs --scale_method awq, --act_stats and --output_format autoawq"
+    if args.search_loss == "output":
+        if not args.fold_scales:
+            return "--search_loss output needs --fold_scales (and so --scale_method awq and --output_format autoawq)"
+        if args.act_samples and args.calib_ids:
+            return "--act_samples and --calib_ids both give token samples: the samples come from one of them"
+        if not args.act_samples and not args.calib_ids:
+            return ("--search_loss output needs token samples: --act_samples FILE (awq_quantizer.calibrate "
+                    "--samples_output), or --calib_ids")
+        if args.calib_ids and args.n_sample_tokens <= 0:
+            return "--n_sample_tokens must be positive"
+    elif args.act_samples:
+        return "--act_samples is read by --search_loss output"
     return None
 
 

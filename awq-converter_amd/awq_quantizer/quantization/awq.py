@@ -17,7 +17,10 @@ include/awq_hip.h awq_quantize_search instead of plain RTN ("mse"/"minmax" stay 
 scale_method="awq" (new value, opt-in) adds quantize_layer_group, the activation-aware
 per-input-channel scale search of include/awq_hip.h awq_act_* (act_search.py), and
 quantize_block, which runs it over the layer groups of a decoder block (block_plan.py) and
-folds 1 / s into the ops producing each input (awq_fold_rows).
+folds 1 / s into the ops producing each input (awq_fold_rows); with token samples of a linear's
+input, quantization_error(samples=) measures a result at the layer's output and
+quantize_layer_group / quantize_block(loss="output") score the search by that error
+(include/awq_hip.h awq_output_error).
 """
 
 import math
@@ -604,7 +607,8 @@ class AWQQuantizer:
     def quantize_layer_group(self, weights: Dict[str, torch.Tensor], activations: Optional[torch.Tensor] = None,
                              *, x_mean: Optional[torch.Tensor] = None, x_sq: Optional[torch.Tensor] = None,
                              packed: bool = True, table: Optional[torch.Tensor] = None, clip: bool = False,
-                             clip_grid: int = 20, clip_max_shrink: float = 0.5) -> dict:
+                             clip_grid: int = 20, clip_max_shrink: float = 0.5, loss: str = "diag",
+                             samples: Optional[torch.Tensor] = None) -> dict:
         """Activation-aware scale search + quantization of linears that read one input
         (scale_method="awq"; include/awq_hip.h awq_act_*, act_search.py).
 
@@ -622,10 +626,26 @@ class AWQQuantizer:
         error is kept.  Packed outputs only.  The return value gains "clip": {"loss_before",
         "loss_after" (the layer group's fp64 loss with candidate 0 / with the winners),
         "clipped_fraction" (groups whose winner is not candidate 0), "per_weight": name -> the same
-        three for that weight, "best_idx": name -> the winners, int32 [rows * G] on the device}."""
+        three for that weight, "best_idx": name -> the winners, int32 [rows * G] on the device}.
+
+        loss="output" scores the same candidates (the table still comes from the statistics) by
+        AWQ's published objective, the layer group's output error on token samples
+        sum_j ||(Q(W_j s) / s - W_j) X^T||^2 (awq_output_error; samples [tokens, in_features],
+        default: `activations`), instead of its diagonal form: every candidate of every weight
+        is quantized into a reused packed buffer and measured.  Same selection rule (first
+        minimum, a NaN loss never wins).  The return value gains "loss": "output", "losses" are
+        the output-space losses, and "diag_losses" / "diag_best" say what the diagonal search
+        would have chosen.  clip=True composes with it; the clip search keeps its x_sq-weighted
+        (diagonal) loss.  loss="diag" (default) is the search described above, unchanged."""
         from .act_search import _check_group, search_layer_group
         if self.scale_method != "awq":
             raise ValueError("quantize_layer_group needs scale_method='awq'")
+        if loss not in ("diag", "output"):
+            raise ValueError(f"loss must be 'diag' or 'output': {loss!r}")
+        if loss == "output":
+            samples = activations if samples is None else samples
+            if samples is None:
+                raise ValueError("loss='output' needs token samples (samples=, or activations=)")
         n_clip = 0
         if clip:
             if not packed:
@@ -645,8 +665,12 @@ class AWQQuantizer:
         sr = search_layer_group(weights, dev, group_size=self.group_size, bits=self.bits, symmetric=self.symmetric,
                                 n_grid=self.search_grid, duo_scaling=self.duo_scaling, activations=activations,
                                 x_mean=x_mean, x_sq=x_sq, table=table, scale_weights=not one_pass)
+        extra = {}
+        if loss == "output":
+            sr = self._output_search(sr, samples)
+            extra = {"loss": "output", "diag_losses": sr["diag_losses"], "diag_best": int(sr["diag_best"].item())}
         if clip:
-            return self._clip_layer_group(weights, sr, clip_grid, n_clip)
+            return dict(self._clip_layer_group(weights, sr, clip_grid, n_clip), **extra)
         results = {}
         for name in weights:
             w = sr["weights"][name]
@@ -661,8 +685,42 @@ class AWQQuantizer:
             results[name] = r
         best = int(sr["best"].item())
         self.logger.info(f"awq search over {list(weights)}: ratio {best}/{self.search_grid}")
-        return {"results": results, "input_scale": sr["input_scale"], "best": best,
-                "ratio": best / self.search_grid, "losses": sr["losses"], "table": sr["table"]}
+        return dict({"results": results, "input_scale": sr["input_scale"], "best": best,
+                     "ratio": best / self.search_grid, "losses": sr["losses"], "table": sr["table"]}, **extra)
+
+    def _output_search(self, sr: dict, samples: torch.Tensor) -> dict:
+        """quantize_layer_group's loss="output": the search result `sr` with losses / best /
+        input_scale taken from the output error on the samples.  Candidate i of every weight:
+        awq_quantize_groups_scaled(w, table[i]) into the weight's reused packed buffer (the
+        apply + quantize pair where that kernel does not take the shape), then awq_output_error
+        with col_scale = table[i] writes the rows' sums into part[i, offset : offset + N];
+        awq_act_search_select adds each candidate's row in fp64 and picks the first minimum."""
+        table = sr["table"]
+        n_grid, K = table.shape
+        ws = sr["weights"]
+        dev = table.device
+        if samples.dim() != 2 or samples.shape[1] != K:
+            raise ValueError(f"samples must be [tokens, {K}], got {tuple(samples.shape)}")
+        dtype = next(iter(ws.values())).dtype
+        xs = _device_input(samples.detach().to(dtype), dev)
+        part = torch.empty((n_grid, sum(w.shape[0] for w in ws.values())), dtype=torch.float32, device=dev)
+        off = 0
+        for w in ws.values():
+            N = w.shape[0]
+            one_pass = _hip.scaled_eligible(w.dtype, N, K, self.group_size) and w.data_ptr() % 16 == 0
+            r = self._packed_outputs(w) if one_pass else None
+            for i in range(n_grid):
+                if one_pass:
+                    _hip.quantize_groups_scaled(w, table[i], self.group_size, self.bits, self.symmetric,
+                                                qweight=r["qweight"], qzeros=r["qzeros"], scales=r["scales"])
+                else:
+                    r = self.quantize_packed(_hip.apply_input_scale(w, table[i]))
+                _hip.output_error(w, self.group_size, self.bits, self.symmetric, _aligned(r["qweight"]), r["qzeros"],
+                                  r["scales"], xs, table[i], ref=False, err_sq=part[i, off:off + N])
+            off += N
+        losses, best, s_best = _hip.act_search_select(part, table)
+        return dict(sr, losses=losses, best=best, input_scale=s_best, scaled=None,
+                    diag_losses=sr["losses"], diag_best=sr["best"])
 
     def _clip_layer_group(self, weights, sr: dict, clip_grid: int, n_clip: int) -> dict:
         """quantize_layer_group's last step with clip=True: every weight through
@@ -709,7 +767,8 @@ class AWQQuantizer:
                          "clipped_fraction": clipped / sum(counts), "per_weight": per, "best_idx": idx}}
 
     def quantize_block(self, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
-                       block, *, clip: bool = False, clip_grid: int = 20, clip_max_shrink: float = 0.5) -> dict:
+                       block, *, clip: bool = False, clip_grid: int = 20, clip_max_shrink: float = 0.5,
+                       samples: Optional[Dict[str, torch.Tensor]] = None, loss: str = "diag") -> dict:
         """Activation-aware quantization of one decoder block with the searched input scales
         folded into the ops that produce each input (block_plan.Block; scale_method="awq").
 
@@ -738,9 +797,18 @@ class AWQQuantizer:
         "input_scale": the fold is done), "folded": name -> folded norm weight / bias,
         "scales": {"<weight>.input_scale": s fp32 [in] for every member, "<weight>.row_scale":
         fp32 [out] for every row-folded producer}, "groups": group -> {"ratio", "losses",
-        "folded", "clip"}}."""
+        "folded", "clip"}}.
+
+        loss="output" (quantize_layer_group's) with samples: group name (attn_in, attn_out, mlp_in,
+        mlp_out) -> token samples [tokens, in] of that group's input, passed to the four calls in
+        the order above.  The samples are the UNFOLDED inputs (what the calibration forward saw):
+        the search's col_scale already accounts for the fold.  A folded group without samples
+        falls back to the diagonal loss with a warning.  Such groups' reports gain "loss", "best"
+        and "diag_best"."""
         if self.scale_method != "awq":
             raise ValueError("quantize_block needs scale_method='awq'")
+        if loss not in ("diag", "output"):
+            raise ValueError(f"loss must be 'diag' or 'output': {loss!r}")
         self._check_mode()
         dev = self.compute_device()
         clip_kw = {"clip": True, "clip_grid": clip_grid, "clip_max_shrink": clip_max_shrink} if clip else {}
@@ -772,12 +840,21 @@ class AWQQuantizer:
             fold = g.foldable and st is not None
             if fold or (clip and st is not None):
                 table = None if fold else torch.ones((self.search_grid, K), dtype=torch.float32, device=dev)
-                out = self.quantize_layer_group(weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw)
+                loss_kw = {}
+                if fold and loss == "output":
+                    smp = (samples or {}).get(g.name)
+                    if smp is None:
+                        self.logger.warning(f"{g.name}: no token samples for loss='output': diagonal loss")
+                    else:
+                        loss_kw = {"loss": "output", "samples": smp}
+                out = self.quantize_layer_group(weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw, **loss_kw)
                 for m, r in out["results"].items():
                     results[m] = {k: v for k, v in r.items() if k != "input_scale"}
                 s = out["input_scale"]
                 report[g.name] = {"ratio": out["ratio"] if fold else None, "losses": out["losses"] if fold else None,
                                   "folded": fold, "clip": out.get("clip")}
+                if loss_kw:
+                    report[g.name].update(loss="output", best=out["best"], diag_best=out["diag_best"])
             else:
                 for m, w in weights.items():
                     results[m] = self.quantize_packed(w)
@@ -886,7 +963,7 @@ class AWQQuantizer:
 
     # ------------------------------------------------------------------ quantization-error report
     def quantization_error(self, tensor: torch.Tensor, result: Dict[str, torch.Tensor],
-                           per_group: bool = False) -> dict:
+                           per_group: bool = False, samples: Optional[torch.Tensor] = None) -> dict:
         """What `result` costs against the original `tensor`: the reference's only quality figure
         (torch.abs(tensor - dequantized).mean(), its test_quantization.py:155-160) and its
         relatives, from one pass over the weights and the PACKED result (include/awq_hip.h
@@ -904,7 +981,17 @@ class AWQQuantizer:
         report is then taken against RN(W * input_scale) in the weight dtype (awq_apply_input_scale),
         i.e. in the scaled domain the checkpoint lives in, and "input_scaled" is True.
         per_group=True adds the device tensors group_abs / group_sq / group_w_sq / group_max (fp32
-        [rows, G]) and group_nonfinite (int32 [rows, G])."""
+        [rows, G]) and group_nonfinite (int32 [rows, G]).
+
+        samples [tokens, in_features] (CPU or device, converted to the weight's dtype) adds what the
+        result costs at the linear's OUTPUT on those inputs (include/awq_hip.h awq_output_error):
+        output_sum_sq = sum (W^ x - W x)^2 and output_ref_sq = sum (W x)^2 over rows and tokens (the
+        fp32 per-row sums added in fp64), output_rel_error = sqrt(output_sum_sq / output_ref_sq),
+        output_snr_db, output_tokens; per_group=True also the device tensors row_output_sq /
+        row_output_ref_sq (fp32 [rows]).  For a result that carries input_scale these are taken in
+        the ORIGINAL domain — the original tensor, w^ = dq / input_scale, unscaled samples: the
+        layer as the model runs it after the fold — while the weight-space figures above stay in
+        the scaled domain.  A shape mismatch raises ValueError before any device work."""
         self._check_input(tensor)
         if tensor.dtype == torch.float64:
             raise RuntimeError("quantization_error: float64 weights are not supported")
@@ -925,8 +1012,11 @@ class AWQQuantizer:
         if in_scale is not None and (tensor.dim() != 2 or tuple(in_scale.shape) != (K,)):
             raise ValueError(f"quantization_error: input_scale {tuple(in_scale.shape)} does not match a 2-D weight "
                              f"[out, {K}] (tensor shape {tuple(tensor.shape)})")
+        if samples is not None and (tensor.dim() != 2 or samples.dim() != 2 or samples.shape[1] != K):
+            raise ValueError(f"quantization_error: samples {tuple(samples.shape)} do not match a 2-D weight "
+                             f"[out, {K}] (tensor shape {tuple(tensor.shape)})")
         dev = self.compute_device()
-        w = _device_input(tensor, dev)
+        w = w_orig = _device_input(tensor, dev)
         if in_scale is not None:     # the result quantizes W * diag(input_scale): measure against that
             w = _hip.apply_input_scale(w, in_scale.to(dev, torch.float32).contiguous())
         scales = scales.to(dev, torch.float16).contiguous()
@@ -953,6 +1043,13 @@ class AWQQuantizer:
         stats, bad, totals = _hip.quant_error(w, rows, K, L, bits, sym, _aligned(qweight), qzeros, scales)
         out = error_report(n, totals.tolist())
         out["input_scaled"] = in_scale is not None
+        if samples is not None:
+            col = in_scale.to(dev, torch.float32).contiguous() if in_scale is not None else None
+            e_sq, r_sq, _ = _hip.output_error(w_orig, L, bits, sym, _aligned(qweight), qzeros, scales,
+                                              _device_input(samples.to(w_orig.dtype), dev), col)
+            out.update(output_report(float(e_sq.double().sum()), float(r_sq.double().sum()), samples.shape[0]))
+            if per_group:
+                out.update(row_output_sq=e_sq, row_output_ref_sq=r_sq)
         if per_group:
             out.update(group_abs=stats[0].view(rows, G), group_sq=stats[1].view(rows, G),
                        group_w_sq=stats[2].view(rows, G), group_max=stats[3].view(rows, G),
@@ -973,6 +1070,20 @@ class AWQQuantizer:
                 self.logger.error(f"Error measuring tensor: {name}, error: {e}")
                 continue
         return out
+
+
+def output_report(err_sq: float, ref_sq: float, tokens: int) -> dict:
+    """The output-space figures from the sums of awq_output_error's err_sq / ref_sq over a tensor's
+    rows — or over a model: the sums add."""
+    if err_sq == 0.0:
+        snr = math.inf
+    elif err_sq != err_sq or ref_sq != ref_sq:
+        snr = math.nan
+    else:
+        snr = 10.0 * math.log10(ref_sq / err_sq) if ref_sq > 0.0 else -math.inf
+    rel = math.sqrt(err_sq / ref_sq) if ref_sq > 0.0 and err_sq >= 0.0 else (0.0 if err_sq == 0.0 else math.nan)
+    return {"output_sum_sq": err_sq, "output_ref_sq": ref_sq, "output_rel_error": rel, "output_snr_db": snr,
+            "output_tokens": int(tokens)}
 
 
 def error_report(numel: int, totals) -> dict:

@@ -24,6 +24,12 @@ and "layout": "autoawq".  With a sidecar the fold itself is audited (fold_audit)
 per layer group, the folded norm weights and producer biases bit for bit.  Every other tensor must
 equal the source's bytes (report key "copied").  Any finding is a "problems" entry and makes the
 return code 1.  Checkpoints written by AutoAWQ itself are out of scope (parity unpinned).
+
+--act_samples FILE (awq_quantizer.calibrate --samples_output): every linear that has token samples
+of its input also gets the output-space figures (quantization_error(samples=): output_sum_sq,
+output_ref_sq, output_rel_error, output_snr_db, output_tokens — for a result with input_scale in
+the original domain; AutoAWQ layout: against the row-folded source), the totals add the sums, and
+a second worst-N list is logged by output_snr_db.  Without the flag the report is unchanged.
 """
 import argparse
 import json
@@ -52,6 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="JSON report path (default: <quantized_dir>/quantization_error.json)")
     p.add_argument("--device", type=str, default="cuda:0", help="GPU the report is computed on")
     p.add_argument("--worst", type=int, default=5, help="log the N worst tensors by snr_db")
+    p.add_argument("--act_samples", type=str, default=None,
+                   help="token samples written by awq_quantizer.calibrate --samples_output: every linear that has "
+                        "samples also gets the output-space figures (output_sum_sq, output_snr_db, ...)")
     p.add_argument("--log_level", type=str, default="INFO")
     return p
 
@@ -103,6 +112,54 @@ def model_totals(entries: Dict[str, dict]) -> dict:
     totals.append(sum(e["nonfinite"] for e in vals))
     out = error_report(sum(e["numel"] for e in vals), totals)
     out["tensors"] = len(vals)
+    with_output = [e for e in vals if "output_sum_sq" in e]
+    if with_output:     # --act_samples: the output-space sums add too
+        from .quantization.awq import output_report
+        o = output_report(math.fsum(e["output_sum_sq"] for e in with_output),
+                          math.fsum(e["output_ref_sq"] for e in with_output), 0)
+        del o["output_tokens"]
+        out.update(o, output_tensors=len(with_output))
+    return out
+
+
+_OUTPUT_KEYS = ("output_sum_sq", "output_ref_sq", "output_rel_error", "output_snr_db", "output_tokens")
+
+
+def measure(error_fn: Callable, w: torch.Tensor, res: Dict[str, torch.Tensor], samples: Optional[torch.Tensor]):
+    """error_fn's report; with token samples of this linear's input also the output-space figures."""
+    return error_fn(w, res) if samples is None else error_fn(w, res, samples=samples)
+
+
+def output_entry(e: dict) -> dict:
+    return {k: e[k] for k in _OUTPUT_KEYS if k in e}
+
+
+def log_worst(entries: Dict[str, dict], n: int, logger) -> None:
+    for name in worst_tensors(entries, n):
+        logger.info(f"worst by snr_db: {name}  {entries[name]['snr_db']:.2f} dB")
+    for name in worst_by_output(entries, n):
+        logger.info(f"worst by output_snr_db: {name}  {entries[name]['output_snr_db']:.2f} dB")
+
+
+def worst_by_output(entries: Dict[str, dict], n: int) -> List[str]:
+    """The n worst tensors by ascending output_snr_db among those measured on samples (NaN first)."""
+    have = [k for k, e in entries.items() if "output_snr_db" in e]
+    return sorted(have, key=lambda k: (0, 0.0) if entries[k]["output_snr_db"] != entries[k]["output_snr_db"]
+                  else (1, entries[k]["output_snr_db"]))[:max(0, n)]
+
+
+def read_samples(args, logger) -> Optional[Dict[str, torch.Tensor]]:
+    """--act_samples: weight name -> samples ({} without the flag); None after logging why not."""
+    path = getattr(args, "act_samples", None)
+    if not path:
+        return {}
+    try:
+        from .calibration import load_act_samples
+        out = load_act_samples(path)
+    except Exception as e:  # noqa: BLE001
+        logger.error(f"--act_samples: cannot read {path}: {e}")
+        return None
+    logger.info(f"Loaded token samples for {len(out)} weights from {path}")
     return out
 
 
@@ -137,6 +194,9 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
     AutoAWQ directories also use import_fn(gemm, group_size, symmetric) (default:
     AWQQuantizer.import_autoawq) and fold_fn(w, s) (default: awq_fold_rows on args.device)."""
     logger = logger or get_logger(name="awq_verify", level=args.log_level)
+    samples = read_samples(args, logger)
+    if samples is None:
+        return 1
     from .model_loading.safetensors_loader import SafetensorsLoader
     try:
         loader = SafetensorsLoader(model_path=args.model_id, logger_level=args.log_level)
@@ -164,7 +224,7 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
 
         return verify_autoawq(args, loader, index, error_fn,
                               import_fn or (lambda gemm, gs, sym: q().import_autoawq(gemm, gs, sym)),
-                              fold_fn or device_fold, logger)
+                              fold_fn or device_fold, logger, samples)
     entries: Dict[str, dict] = {}
     problems: Dict[str, str] = {}
     skipped: Dict[str, str] = {}
@@ -181,7 +241,7 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
                 logger.error(f"{name}: {problems[name]}")
                 continue
             try:
-                e = error_fn(loader.read(info), res)
+                e = measure(error_fn, loader.read(info), res, samples.get(name))
             except IndexError as ex:   # a small-tensor result (0-d / 1-d scales): not a group result
                 skipped[name] = str(ex)
                 logger.warning(f"{name}: skipped ({ex})")
@@ -194,6 +254,7 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
                                                "mean_abs_error", "mse", "max_abs_error", "snr_db")}
             # --scale_method awq --act_stats: measured against W * diag(input_scale) (quantization_error)
             entries[name]["input_scaled"] = "input_scale" in res
+            entries[name].update(output_entry(e))
             logger.info(f"{name}: mean_abs_error {e['mean_abs_error']:.6g}  max {e['max_abs_error']:.6g}  "
                         f"snr {e['snr_db']:.2f} dB  nonfinite {e['nonfinite']}")
     except Exception as e:  # noqa: BLE001
@@ -201,8 +262,7 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
         return 1
     finally:
         loader.close()
-    for name in worst_tensors(entries, args.worst):
-        logger.info(f"worst by snr_db: {name}  {entries[name]['snr_db']:.2f} dB")
+    log_worst(entries, args.worst, logger)
     path = args.report or os.path.join(args.quantized_dir, "quantization_error.json")
     report = write_report(path, entries, problems, {"model_id": args.model_id, "quantized_dir": args.quantized_dir},
                           skipped)
@@ -341,7 +401,8 @@ def audited_tensors(shapes: Dict[str, Tuple[int, ...]], model_type: Optional[str
 
 
 def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], error_fn: Callable,
-                   import_fn: Callable, fold_fn: Callable, logger) -> int:
+                   import_fn: Callable, fold_fn: Callable, logger,
+                   samples: Optional[Dict[str, torch.Tensor]] = None) -> int:
     """verify() for an --output_format autoawq directory (see the module docstring).
     import_fn(gemm, group_size, symmetric) -> quantize_packed()-shaped dict; fold_fn(w, s) = fold_rows."""
     from safetensors import safe_open
@@ -406,13 +467,14 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
                 in_scale = sidecar.get(f"{name}.input_scale")
                 if in_scale is not None:
                     res = dict(res, input_scale=in_scale)
-                e = error_fn(w, res)
+                e = measure(error_fn, w, res, (samples or {}).get(name))
             except Exception as ex:  # noqa: BLE001
                 problem(name, f"{type(ex).__name__}: {ex}")
                 continue
             entries[name] = {k: e[k] for k in _ENTRY_KEYS}
             entries[name].update(input_scaled=in_scale is not None, row_folded=row_scale is not None,
                                  layout="autoawq")
+            entries[name].update(output_entry(e))
             logger.info(f"{name}: mean_abs_error {e['mean_abs_error']:.6g}  max {e['max_abs_error']:.6g}  "
                         f"snr {e['snr_db']:.2f} dB  nonfinite {e['nonfinite']}")
         judged = set()
@@ -448,8 +510,7 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
     finally:
         loader.close()
         del handles
-    for name in worst_tensors(entries, args.worst):
-        logger.info(f"worst by snr_db: {name}  {entries[name]['snr_db']:.2f} dB")
+    log_worst(entries, args.worst, logger)
     report = write_report(path, entries, problems, echo, skipped,
                           extra={"layout": "autoawq", "copied": copied, "fold_audited": has_sidecar})
     t = report["totals"]

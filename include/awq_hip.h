@@ -334,6 +334,45 @@ int awq_quant_error(const void* w, int dtype, int64_t rows, int64_t K, int64_t g
                     const int32_t* qweight, const int32_t* qzeros, const uint16_t* scales, float* group_stats,
                     int32_t* group_nonfinite, double* work, double* totals, void* stream);
 
+/* ---- Output-space error on token samples (additive to ABI 17; beyond the reference: it replaces
+ * no reference function) ----
+ * What the packed result (qweight / qzeros / scales above, row-major) costs at a linear's OUTPUT on
+ * calibration samples x [T, K] (dtype D of w, row stride x_row_stride >= K elements), against the
+ * original weights w [N, K] (D = bf16 / fp16 / fp32; fp64: AWQ_EUNSUPPORTED).  Per element:
+ *   dq = fp32(fp16(fp16(q - z) * s))                         (awq_quant_error's, awq_dequantize_packed's)
+ *   w^ = dq if col_scale is NULL, else RN_f32(dq / col_scale[k])   (IEEE division; col_scale fp32 [K]:
+ *        the input scale a result of W * diag(s) was quantized with, so w^ is in w's own domain)
+ *   d  = RN_f32(w^ - fp32(w)), no contraction.
+ * E[n, t] = sum_k d[n, k] x[t, k], R[n, t] = sum_k w[n, k] x[t, k];
+ * err_sq[n] = sum_t E^2, ref_sq[n] = sum_t R^2 (ref_sq may be NULL); err [N, T], when not NULL,
+ * receives E itself.  Nothing is masked: a non-finite d, w or x makes the sums that contain it
+ * non-finite, as IEEE arithmetic gives.
+ * Accuracy: the order of the sum over k is the implementation's (the matrix core's), so the contract
+ * is a bound: |E - E_exact| <= eps_K * sum_k |d| |x| with eps_K = 2^-17 + K 2^-22 (d enters as the two
+ * bf16 terms d_hi = RN_bf16(d), d_lo = RN_bf16(d - d_hi): within 2^-17 |d| of d; the products are exact,
+ * 2 K of them accumulate in fp32), the same for R with |w| for |d|; the sum over t adds at most
+ * (T + 1) 2^-24 relative on the computed E^2.  No floating-point atomics: every (128-token tile, row)
+ * writes one fp32 partial to `work` and a second kernel adds the tiles in ascending order, so the
+ * results are the same bits from run to run.
+ * Kernels: bf16 with group_size 32 / 64 / 128 / 256, 16-B aligned w / x / qweight, x_row_stride % 8
+ * == 0 (and K, x_row_stride < 2^22): v_mfma_f32_32x32x16_bf16 on the hi / lo split; everything else:
+ * v_mfma_f32_16x16x4_f32 on f32 operands.
+ * Refused: bits other than 4 / 8, x_row_stride < K (AWQ_EINVAL); a group_size that is not a power of
+ * two in [8, 512], K % group_size != 0, N K, N T or T x_row_stride above 2^60 (AWQ_EUNSUPPORTED).
+ * N, K or T of 0: AWQ_OK, nothing is read or written. */
+
+/* bytes of the workspace awq_output_error needs: fp32 [2][ceil(T / 128)][N] (0 for an empty or
+ * refused shape) */
+int64_t awq_output_error_work_bytes(int64_t N, int64_t T);
+int awq_output_error(const void* w, int dtype, int64_t N, int64_t K, int64_t group_size, int bits, int symmetric,
+                     const int32_t* qweight, const int32_t* qzeros, const uint16_t* scales,
+                     const float* col_scale,            /* [K] or NULL (= 1) */
+                     const void* x, int64_t T, int64_t x_row_stride,   /* samples [T, K] of `dtype`, stride in elements */
+                     void* work, float* err_sq,         /* [N] */
+                     float* ref_sq,                     /* [N] or NULL */
+                     float* err,                        /* [N, T] or NULL */
+                     void* stream);
+
 /* ---- Host streaming pipeline ----------------------------------
  * Replaces the CLI's read -> quantize -> collect loop (reference main.py:216-392, which
  * loads every file whole and then quantizes tensor by tensor): tensors are pread from their
