@@ -13,14 +13,19 @@ x_mean[k]^r), quantizes W·diag(s_i), undoes s_i, and scores the result with
 Σ_k E[x_k²] Σ_n (Ŵ - W)²_nk, the diagonal form of AutoAWQ's output MSE.  The winner's
 W·diag(s) is quantized with the regular kernels and s is returned so the caller folds
 1/s into whatever produces x (a norm's weight, the previous linear's rows).
+
+search_layer_group is the search alone.  The functions that take the quantizer `q` are
+AWQQuantizer's quantize_layer_group (with its output-space search and clip step) and
+quantize_block; the methods' docstrings say what they take and return.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
 from .. import _hip
+from ..layout import aligned, device_input
 
 ACT_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 
@@ -83,3 +88,234 @@ def search_layer_group(weights: Dict[str, torch.Tensor], device: torch.device, *
     scaled = {name: _hip.apply_input_scale(w, s_best) for name, w in zip(weights, ws)} if scale_weights else None
     return {"x_mean": x_mean, "x_sq": x_sq, "w_mean": w_mean, "table": table, "losses": losses, "best": best,
             "input_scale": s_best, "weights": dict(zip(weights, ws)), "scaled": scaled}
+
+
+def _check_args(q, what: str, loss: str) -> None:
+    """What quantize_layer_group and quantize_block refuse first."""
+    if q.scale_method != "awq":
+        raise ValueError(f"{what} needs scale_method='awq'")
+    if loss not in ("diag", "output"):
+        raise ValueError(f"loss must be 'diag' or 'output': {loss!r}")
+
+
+def _quantize_scaled(q, w: torch.Tensor, s: torch.Tensor, one_pass: bool, out: Optional[dict] = None,
+                     scaled: Optional[torch.Tensor] = None) -> dict:
+    """W * diag(s) as a quantize_packed() result.  `one_pass` (the shape is scaled_eligible) and a
+    16-B aligned base: awq_quantize_groups_scaled, the scaled copy is never written, into `out`
+    (an earlier return value whose buffers are reused) or fresh buffers.  Otherwise the copy
+    (`scaled`, if the caller has it), then quantize_packed."""
+    if one_pass and w.data_ptr() % 16 == 0:
+        r = out if out is not None else q._packed_outputs(w)
+        _hip.quantize_groups_scaled(w, s, q.group_size, q.bits, q.symmetric,
+                                    qweight=r["qweight"], qzeros=r["qzeros"], scales=r["scales"])
+        return r
+    return q.quantize_packed(scaled if scaled is not None else _hip.apply_input_scale(w, s))
+
+
+def quantize_layer_group(q, weights: Dict[str, torch.Tensor], activations: Optional[torch.Tensor] = None,
+                         *, x_mean: Optional[torch.Tensor] = None, x_sq: Optional[torch.Tensor] = None,
+                         packed: bool = True, table: Optional[torch.Tensor] = None, clip: bool = False,
+                         clip_grid: int = 20, clip_max_shrink: float = 0.5, loss: str = "diag",
+                         samples: Optional[torch.Tensor] = None) -> dict:
+    """The search over one layer group, then its weights quantized as W * diag(input_scale)."""
+    _check_args(q, "quantize_layer_group", loss)
+    if loss == "output":
+        samples = activations if samples is None else samples
+        if samples is None:
+            raise ValueError("loss='output' needs token samples (samples=, or activations=)")
+    n_clip = 0
+    if clip:
+        if not packed:
+            raise ValueError("clip=True writes packed outputs only (packed=False is not available)")
+        if isinstance(clip_grid, bool) or not isinstance(clip_grid, int) or clip_grid < 1:
+            raise ValueError(f"clip_grid must be a positive integer: {clip_grid}")
+        if not 0.0 <= float(clip_max_shrink) <= 1.0:
+            raise ValueError(f"clip_max_shrink must be in [0, 1]: {clip_max_shrink}")
+        n_clip = min(clip_grid, max(1, int(clip_max_shrink * clip_grid)))
+    _check_group(weights, q.group_size)
+    q._check_mode()
+    dev = q.compute_device()
+    # packed outputs of eligible shapes take _quantize_scaled's one pass: the search need not write the copies
+    one_pass = packed and (clip or all(
+        _hip.scaled_eligible(w.dtype, w.shape[0], w.shape[1], q.group_size) for w in weights.values()))
+    sr = search_layer_group(weights, dev, group_size=q.group_size, bits=q.bits, symmetric=q.symmetric,
+                            n_grid=q.search_grid, duo_scaling=q.duo_scaling, activations=activations,
+                            x_mean=x_mean, x_sq=x_sq, table=table, scale_weights=not one_pass)
+    extra = {}
+    if loss == "output":
+        sr = output_search(q, sr, samples)
+        extra = {"loss": "output", "diag_losses": sr["diag_losses"], "diag_best": int(sr["diag_best"].item())}
+    if clip:
+        return dict(clip_layer_group(q, weights, sr, clip_grid, n_clip), **extra)
+    results, s, scaled = {}, sr["input_scale"], sr["scaled"] or {}
+    for name in weights:
+        w = sr["weights"][name]
+        if packed:
+            r = _quantize_scaled(q, w, s, one_pass, scaled=scaled.get(name))
+        else:                                     # RTN of W * diag(s), the reference's result dict
+            r = q._quantize_device(scaled[name] if name in scaled else _hip.apply_input_scale(w, s))
+        r["input_scale"] = s
+        results[name] = r
+    best = int(sr["best"].item())
+    q.logger.info(f"awq search over {list(weights)}: ratio {best}/{q.search_grid}")
+    return dict({"results": results, "input_scale": s, "best": best,
+                 "ratio": best / q.search_grid, "losses": sr["losses"], "table": sr["table"]}, **extra)
+
+
+def output_search(q, sr: dict, samples: torch.Tensor) -> dict:
+    """quantize_layer_group's loss="output": the search result `sr` with losses / best /
+    input_scale taken from the output error on the samples.  Candidate i of every weight:
+    awq_quantize_groups_scaled(w, table[i]) into the weight's reused packed buffer (the
+    apply + quantize pair where that kernel does not take the shape), then awq_output_error
+    with col_scale = table[i] writes the rows' sums into part[i, offset : offset + N];
+    awq_act_search_select adds each candidate's row in fp64 and picks the first minimum."""
+    table = sr["table"]
+    n_grid, K = table.shape
+    ws = sr["weights"]
+    dev = table.device
+    if samples.dim() != 2 or samples.shape[1] != K:
+        raise ValueError(f"samples must be [tokens, {K}], got {tuple(samples.shape)}")
+    dtype = next(iter(ws.values())).dtype
+    xs = device_input(samples.detach().to(dtype), dev)
+    part = torch.empty((n_grid, sum(w.shape[0] for w in ws.values())), dtype=torch.float32, device=dev)
+    off = 0
+    for w in ws.values():
+        N = w.shape[0]
+        one_pass = _hip.scaled_eligible(w.dtype, N, K, q.group_size)
+        r = None                  # (one pass: the first candidate's buffers take the others too)
+        for i in range(n_grid):
+            r = _quantize_scaled(q, w, table[i], one_pass, out=r)
+            _hip.output_error(w, q.group_size, q.bits, q.symmetric, aligned(r["qweight"]), r["qzeros"],
+                              r["scales"], xs, table[i], ref=False, err_sq=part[i, off:off + N])
+        off += N
+    losses, best, s_best = _hip.act_search_select(part, table)
+    return dict(sr, losses=losses, best=best, input_scale=s_best, scaled=None,
+                diag_losses=sr["losses"], diag_best=sr["best"])
+
+
+def clip_layer_group(q, weights, sr: dict, clip_grid: int, n_clip: int) -> dict:
+    """quantize_layer_group's last step with clip=True: every weight through
+    awq_quantize_clip_scaled with the search's input scale, its reciprocals and x_sq; the
+    groups' losses of all weights meet in one [2, total groups] buffer, summed in fp64 by
+    awq_act_search_select (before = candidate 0, after = the winners)."""
+    s, x_sq = sr["input_scale"], sr["x_sq"]
+    K = s.numel()
+    G = K // q.group_size
+    rs = _hip.act_recip_table(s.reshape(1, K)).reshape(K)
+    names = list(weights)
+    counts = [sr["weights"][n].shape[0] * G for n in names]
+    loss = torch.empty((2, sum(counts)), dtype=torch.float32, device=s.device)
+    results, idx, off = {}, {}, 0
+    for name, cnt in zip(names, counts):
+        w = sr["weights"][name]
+        r = q._packed_outputs(w)
+        idx[name] = torch.empty(cnt, dtype=torch.int32, device=s.device)
+        _hip.quantize_clip_scaled(w, s, x_sq, q.group_size, q.bits, q.symmetric, clip_grid, n_clip,
+                                  rscale=rs, qweight=r["qweight"], qzeros=r["qzeros"], scales=r["scales"],
+                                  best_idx=idx[name], group_loss=loss, loss_offset=off)
+        r["input_scale"] = s
+        results[name] = r
+        off += cnt
+    # (the select kernel also copies the winning row of a table: two rows of s keep that in range)
+    two = s.reshape(1, K).expand(2, K).contiguous()
+    total, _, _ = _hip.act_search_select(loss, two)
+    total = total.cpu()
+    per, off, clipped = {}, 0, 0
+    for name, cnt in zip(names, counts):
+        one, _, _ = _hip.act_search_select(loss[:, off:off + cnt].contiguous(), two)
+        one = one.cpu()
+        nz = int((idx[name] != 0).sum().item())
+        per[name] = {"loss_before": float(one[0]), "loss_after": float(one[1]), "clipped_fraction": nz / cnt}
+        q.logger.info(f"awq clip {name}: clipped {nz / cnt:.1%} of {cnt} groups, loss "
+                         f"{float(one[0]):.6g} -> {float(one[1]):.6g}")
+        clipped += nz
+        off += cnt
+    best = int(sr["best"].item())
+    q.logger.info(f"awq search over {names}: ratio {best}/{q.search_grid}, clip {n_clip}/{clip_grid}")
+    return {"results": results, "input_scale": s, "best": best, "ratio": best / q.search_grid,
+            "losses": sr["losses"], "table": sr["table"],
+            "clip": {"loss_before": float(total[0]), "loss_after": float(total[1]),
+                     "clipped_fraction": clipped / sum(counts), "per_weight": per, "best_idx": idx}}
+
+
+def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
+                   block, *, clip: bool = False, clip_grid: int = 20, clip_max_shrink: float = 0.5,
+                   samples: Optional[Dict[str, torch.Tensor]] = None, loss: str = "diag") -> dict:
+    """One decoder block: the out groups, their row folds, the in groups, their norm folds."""
+    _check_args(q, "quantize_block", loss)
+    q._check_mode()
+    dev = q.compute_device()
+    clip_kw = {"clip": True, "clip_grid": clip_grid, "clip_max_shrink": clip_max_shrink} if clip else {}
+    results, folded, scales, report = {}, {}, {}, {}
+    current: Dict[str, torch.Tensor] = {}     # device tensors, row-folded producers replaced
+
+    def dev_t(name: str) -> torch.Tensor:
+        if name not in current:
+            if name not in tensors:
+                raise KeyError(f"quantize_block: tensor {name} is missing")
+            current[name] = tensors[name].detach().to(dev).contiguous()
+        return current[name]
+
+    def group_stats(g):
+        have = [m for m in g.members if m in stats]
+        if not have:
+            return None
+        first = stats[have[0]]
+        for m in have[1:]:
+            if not (torch.equal(stats[m][0], first[0]) and torch.equal(stats[m][1], first[1])):
+                q.logger.warning(f"{m}: activation statistics differ from {have[0]}'s (same input): "
+                                    f"using {have[0]}'s for the {g.name} group")
+        return first
+
+    def run(g) -> Optional[torch.Tensor]:
+        weights = {m: dev_t(m) for m in g.members}
+        st = group_stats(g)
+        K = next(iter(weights.values())).shape[1]
+        fold = g.foldable and st is not None
+        if fold or (clip and st is not None):
+            table = None if fold else torch.ones((q.search_grid, K), dtype=torch.float32, device=dev)
+            loss_kw = {}
+            if fold and loss == "output":
+                smp = (samples or {}).get(g.name)
+                if smp is None:
+                    q.logger.warning(f"{g.name}: no token samples for loss='output': diagonal loss")
+                else:
+                    loss_kw = {"loss": "output", "samples": smp}
+            out = q.quantize_layer_group(weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw, **loss_kw)
+            for m, r in out["results"].items():
+                results[m] = {k: v for k, v in r.items() if k != "input_scale"}
+            s = out["input_scale"]
+            report[g.name] = {"ratio": out["ratio"] if fold else None, "losses": out["losses"] if fold else None,
+                              "folded": fold, "clip": out.get("clip")}
+            if loss_kw:
+                report[g.name].update(loss="output", best=out["best"], diag_best=out["diag_best"])
+        else:
+            for m, w in weights.items():
+                results[m] = q.quantize_packed(w)
+            s = torch.ones(K, dtype=torch.float32, device=dev)
+            report[g.name] = {"ratio": None, "losses": None, "folded": False, "clip": None}
+        for m in g.members:
+            scales[f"{m}.input_scale"] = s
+        return s if fold else None
+
+    groups = block.groups
+    for gname in ("attn_out", "mlp_out"):
+        g = groups.get(gname)
+        if g is None:
+            continue
+        s_out = run(g)
+        if s_out is None:
+            continue
+        pw = g.producers[0]
+        current[pw] = _hip.fold_rows(dev_t(pw), s_out)            # a new device tensor: the source stays
+        scales[f"{pw}.row_scale"] = s_out
+        for pb in g.producers[1:]:
+            folded[pb] = _hip.fold_rows(dev_t(pb), s_out)
+    for gname in ("attn_in", "mlp_in"):
+        g = groups.get(gname)
+        if g is None:
+            continue
+        s_in = run(g)
+        if s_in is not None:
+            folded[g.producers[0]] = _hip.fold_rows(dev_t(g.producers[0]), s_in)
+    return {"results": results, "folded": folded, "scales": scales, "groups": report}

@@ -12,6 +12,9 @@ from typing import Dict, Optional
 import torch
 
 from .. import _hip
+from ..layout import device_input, packed_shapes, result_meta, rows_k
+
+REFERENCE_KEYS = ("tensor_q", "scales", "zero_points", "bits", "group_size", "symmetric")   # awq.py:409-416
 
 
 class PackedBatch:
@@ -43,7 +46,6 @@ class PackedBatch:
         _hip.require_device(dev)
         self.device = dev
         self.inputs = inputs
-        per = 32 // bits
         self.out = {}
         descs = []
         for name in self.names:
@@ -51,19 +53,18 @@ class PackedBatch:
             if x.device != dev or x.dtype != self.dtype or not x.is_contiguous():
                 raise ValueError(f"{name}: inputs must be contiguous {self.dtype} tensors on {dev} (one dtype "
                                  f"per batch)")
-            rows = 1 if x.dim() <= 1 else x.shape[0]
-            K = x.numel() // rows
+            sh = packed_shapes(x.shape, gs, bits)     # padded rows: the tail group counts (awq.py:337-339)
+            rows, K = sh["rows"], sh["K"]
             if not _hip.ragged_eligible(x.dtype, rows, K, gs):
                 raise ValueError(f"{name}: shape {tuple(x.shape)} is not eligible for a ragged launch "
                                  f"(group_size {gs})")
-            G = -(-K // gs)          # padded rows: the tail group counts (awq.py:337-339)
-            o = {"scales": torch.empty((rows, G), dtype=torch.float16, device=dev)}
+            o = {"scales": torch.empty(sh["scales"], dtype=torch.float16, device=dev)}
             if packed:
-                o["qweight"] = torch.empty((rows, -(-K // per)), dtype=torch.int32, device=dev)
-                o["qzeros"] = torch.empty((rows, -(-G // per)), dtype=torch.int32, device=dev)
+                o["qweight"] = torch.empty(sh["qweight"], dtype=torch.int32, device=dev)
+                o["qzeros"] = torch.empty(sh["qzeros"], dtype=torch.int32, device=dev)
             if parity:
                 o["tensor_q"] = torch.empty(x.shape, dtype=torch.int32, device=dev)
-                o["zero_points"] = torch.empty((rows, G), dtype=torch.int32, device=dev)
+                o["zero_points"] = torch.empty(sh["scales"], dtype=torch.int32, device=dev)
             self.out[name] = o
             p = lambda k: o[k].data_ptr() if k in o else None
             descs.append(_hip.TensorDesc(x.data_ptr(), rows, K, p("qweight"), p("qzeros"), p("scales"),
@@ -89,15 +90,9 @@ class PackedBatch:
                              search=self.search)
 
     def results(self) -> Dict[str, Dict[str, torch.Tensor]]:
-        res = {}
-        for name in self.names:
-            o = dict(self.out[name])
-            o["bits"] = torch.tensor(self.bits, dtype=torch.int32)
-            o["group_size"] = torch.tensor(self.group_size, dtype=torch.int32)
-            o["symmetric"] = torch.tensor(self.symmetric, dtype=torch.bool)
-            o["shape"] = torch.tensor(list(self.inputs[name].shape), dtype=torch.int64)
-            res[name] = o
-        return res
+        return {name: dict(self.out[name], **result_meta(self.bits, self.group_size, self.symmetric,
+                                                         self.inputs[name].shape))
+                for name in self.names}
 
     def algorithmic_bytes(self) -> int:
         """HBM bytes one launch must move: bf16 in + packed out (+ parity outputs)."""
@@ -107,3 +102,63 @@ class PackedBatch:
             for t in self.out[name].values():
                 b += t.numel() * t.element_size()
         return b
+
+
+def quantize_model_batched(q, tensors: Dict[str, torch.Tensor], packed: bool) -> Dict[str, Dict[str, torch.Tensor]]:
+    """AWQQuantizer.quantize_model_packed (packed) / quantize_model_device(packed=False): the
+    ragged-eligible tensors in one PackedBatch per dtype, the rest one by one, failures logged
+    and skipped, results in input order.  The two differ in when a tensor is refused and when
+    the one-by-one tensors run; each branch on `packed` below is one such difference."""
+    one = q.quantize_packed if packed else q._quantize_device
+    out, eligible, rest = {}, {}, {}
+
+    def single(name, t):
+        try:
+            out[name] = one(t)
+        except Exception as e:
+            q.logger.error(f"Error quantizing tensor: {name}, error: {e}")
+
+    if packed:
+        q._check_mode()          # raises out of the call; unpacked: per tensor, logged (the reference's skip)
+    for name, t in tensors.items():
+        try:
+            q._check_input(t)
+            if not packed:
+                q._check_mode()
+        except Exception as e:  # reference semantics: skip and continue
+            q.logger.error(f"Error quantizing tensor: {name}, error: {e}")
+            continue
+        if packed and t.numel() < q.group_size:      # (unpacked: quantize()'s small-tensor path)
+            q.logger.error(f"Error quantizing tensor: {name}, error: numel < group_size")
+            continue
+        rows, K = rows_k(t.shape)
+        if t.numel() >= q.group_size and _hip.ragged_eligible(t.dtype, rows, K, q.group_size):
+            eligible[name] = t
+        elif packed:
+            rest[name] = t       # after the batches
+        else:
+            single(name, t)      # before them
+    if eligible:
+        dev = q.compute_device()
+        for dt in (torch.bfloat16, torch.float16, torch.float32):   # one ragged launch per input dtype
+            part = {k: device_input(v, dev) for k, v in eligible.items() if v.dtype == dt}
+            if not part:
+                continue
+            try:
+                batch = PackedBatch(part, bits=q.bits, symmetric=q.symmetric, parity=not packed, packed=packed,
+                                    group_size=q.group_size, search=q._search_args())
+                batch.run()
+                res = batch.results()
+            except Exception as e:   # the batch as a whole failed: every tensor on its own
+                q.logger.error(f"ragged launch of {len(part)} tensors failed ({e}); quantizing them one by one")
+                if packed:
+                    rest.update(part)
+                else:
+                    for name, t in part.items():
+                        single(name, t)
+                continue
+            for name, r in res.items():
+                out[name] = r if packed else {k: r[k] for k in REFERENCE_KEYS}
+    for name, t in rest.items():
+        single(name, t)
+    return {k: out[k] for k in tensors if k in out}

@@ -38,6 +38,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from .layout import row_shapes
+
 ALIGN = 256                  # byte alignment of every output field inside a region
 _ES = {torch.int32: 4, torch.float16: 2}
 HOST_RING_FLOOR = 512 << 20  # smallest host ring tried when the output does not fit it
@@ -47,13 +49,12 @@ DEV_RING_FLOOR = 1 << 30
 def out_fields(shape, rows: int, K: int, gs: int, bits: int, packed: bool):
     """(field, shape, dtype) of one tensor's results: the packed format (quantize_packed) or
     the reference's result dict (awq.py:409-416)."""
-    per = 32 // bits
-    G = -(-K // gs)
+    sh = row_shapes(rows, K, gs, bits)
     if packed:
-        return [("qweight", (rows, -(-K // per)), torch.int32), ("qzeros", (rows, -(-G // per)), torch.int32),
-                ("scales", (rows, G), torch.float16)]
-    return [("tensor_q", tuple(shape), torch.int32), ("scales", (rows, G), torch.float16),
-            ("zero_points", (rows, G), torch.int32)]
+        return [("qweight", sh["qweight"], torch.int32), ("qzeros", sh["qzeros"], torch.int32),
+                ("scales", sh["scales"], torch.float16)]
+    return [("tensor_q", tuple(shape), torch.int32), ("scales", sh["scales"], torch.float16),
+            ("zero_points", sh["scales"], torch.int32)]
 
 
 def region_layout(shape, rows: int, K: int, gs: int, bits: int, packed: bool):
