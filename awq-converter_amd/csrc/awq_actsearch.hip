@@ -1145,7 +1145,7 @@ hipError_t launch_weight_colsum(const void* w, int dtype, int64_t R, int64_t K, 
     const int lpg = (int)(L / 8);
     const int64_t G = K / L;
     const int64_t items = ((R + (64 / lpg) - 1) / (64 / lpg)) * G;
-    AWQ_DT_SWITCH(dtype, hipLaunchKernelGGL((group_absmax_kernel<D>), dim3(blocks_for(items, 4, 256 * 64)),
+    AWQ_DT_SWITCH(dtype, hipLaunchKernelGGL((group_absmax_kernel<D>), dim3(diag_cap(blocks_for(items, 4, 256 * 64))),
                                             dim3(256), 0, stream, w, R, K, lpg, gmax))
     if (hipError_t e = hipPeekAtLastError()) return e;
     const int64_t nblk = (R + kRowBlock - 1) / kRowBlock;
@@ -1235,7 +1235,7 @@ hipError_t launch_act_losses(const void* w, int dtype, int64_t R, int64_t K, int
     const int qmax = symmetric ? (1 << (bits - 1)) - 1 : (1 << bits) - 1;
     const int lpg = (int)(L / 8);
     const int64_t items = ((R + (64 / lpg) - 1) / (64 / lpg)) * (K / L);
-    const unsigned grid = blocks_for(items, 4, 256 * 32);
+    const unsigned grid = diag_cap(blocks_for(items, 4, 256 * 32));
 #define AWQ_LOSS_LAUNCH(LP, SY, EP, LPA)                                                                       \
     AWQ_DT_SWITCH(dtype, hipLaunchKernelGGL((act_loss_kernel<D, LP, SY, EP>), dim3(g2), dim3(256), 0, stream, w, R, \
                                             K, LPA, qmin, qmax, table, rtable, n_grid, x_sq, part, stride))
@@ -1243,7 +1243,7 @@ hipError_t launch_act_losses(const void* w, int dtype, int64_t R, int64_t K, int
     if (symmetric) { AWQ_LOSS_LAUNCH(LP, true, EP, LPA) } else { AWQ_LOSS_LAUNCH(LP, false, EP, LPA) }
     // the streaming group sizes 32 / 64 / 128 / 256: 16 elements per lane, gs / 16 lanes per
     // group as a constant (twice the groups per wave: half the items)
-    const unsigned g2 = (lpg >= 4 && lpg <= 32) ? blocks_for((items + 1) / 2, 4, 256 * 32) : grid;
+    const unsigned g2 = (lpg >= 4 && lpg <= 32) ? diag_cap(blocks_for((items + 1) / 2, 4, 256 * 32)) : grid;
     switch (lpg) {
     case 4: AWQ_LOSS_SYM(2, 16, 2) break;
     case 8: AWQ_LOSS_SYM(4, 16, 4) break;
@@ -1273,12 +1273,12 @@ hipError_t launch_apply_scale(const void* w, int dtype, int64_t R, int64_t K, co
                               hipStream_t stream) {
     const bool vec = K % 8 == 0 && ((uintptr_t)w | (uintptr_t)s | (uintptr_t)out) % 16 == 0;
     if (!vec) {
-        const unsigned g1 = blocks_for(R * K, 256, 256 * 64);
+        const unsigned g1 = diag_cap(blocks_for(R * K, 256, 256 * 64));
         AWQ_DT_SWITCH(dtype, hipLaunchKernelGGL((apply_scale_any_kernel<D>), dim3(g1), dim3(256), 0, stream, w, R, K,
                                                 s, out))
         return hipPeekAtLastError();
     }
-    const unsigned grid = blocks_for(R * K / 8, 256, 256 * 64);
+    const unsigned grid = diag_cap(blocks_for(R * K / 8, 256, 256 * 64));
     AWQ_DT_SWITCH(dtype, hipLaunchKernelGGL((apply_scale_kernel<D>), dim3(grid), dim3(256), 0, stream, w, R, K, s,
                                             out))
     return hipPeekAtLastError();

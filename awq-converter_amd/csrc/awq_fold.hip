@@ -124,7 +124,7 @@ hipError_t launch_fold_rows(const void* w, int dtype, int64_t rows, int64_t K, c
     }
     int64_t blocks = (total + 255) / 256;
     if (blocks > 65536) blocks = 65536;   // grid-stride beyond
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(diag_cap((unsigned)blocks)), block(256);
     if (dtype == AWQ_DTYPE_BF16)
         hipLaunchKernelGGL(awq_fold_any_kernel<FmtBF16>, grid, block, 0, stream, w, out, row_scale, rows, K);
     else if (dtype == AWQ_DTYPE_F16)

@@ -656,7 +656,7 @@ inline unsigned grid_for(int64_t work, int64_t per_block, int64_t cap) {
     int64_t b = (work + per_block - 1) / per_block;
     if (b < 1) b = 1;
     if (b > cap) b = cap;
-    return (unsigned)b;
+    return diag_cap((unsigned)b);   // (every kernel launched through here is grid-stride)
 }
 
 }  // namespace

@@ -183,6 +183,13 @@ inline const awq_tuning& tuning() {
     return kDefaults;
 }
 #endif
+// the grid of a capped launch whose kernel walks its work in a grid-stride loop: min(grid,
+// tuning().max_blocks) in the diagnostics build (tests then reach the loop's later trips at
+// small shapes), grid itself in the product build (max_blocks is the constant 0)
+inline unsigned diag_cap(unsigned grid) {
+    const int32_t m = tuning().max_blocks;
+    return (m > 0 && grid > (unsigned)m) ? (unsigned)m : grid;
+}
 
 // host helpers of the extern "C" entry points, defined once in awq_capi.hip.  The message is the
 // calling thread's awq_last_error(); each returns the code it is given.

@@ -402,7 +402,7 @@ extern "C" int awq_output_error(const void* w, int dtype, int64_t N, int64_t K, 
                       aligned(qweight, 16) && x_row_stride % 8 == 0 && K < kMaxDesc && x_row_stride < kMaxDesc;
     if (fast) {
         const int64_t tiles = (N + kRowTile - 1) / kRowTile * tts;
-        const unsigned grid = (unsigned)std::min<int64_t>(tiles, 0x7FFFFFFF);
+        const unsigned grid = diag_cap((unsigned)std::min<int64_t>(tiles, 0x7FFFFFFF));
         const int shift = __builtin_ctzll((unsigned long long)group_size);
 #define AWQ_OE(BITS, DIV, REF)                                                                                     \
     hipLaunchKernelGGL((outerr_mfma_kernel<BITS, DIV, REF>), dim3(grid), dim3(256), 0, st, w, qwp, qzp, scales,      \
@@ -418,7 +418,7 @@ extern "C" int awq_output_error(const void* w, int dtype, int64_t N, int64_t K, 
 #undef AWQ_OE
     } else {
         const int64_t tiles = (N + kGenRows - 1) / kGenRows * tts;
-        const unsigned grid = (unsigned)std::min<int64_t>(tiles, 0x7FFFFFFF);
+        const unsigned grid = diag_cap((unsigned)std::min<int64_t>(tiles, 0x7FFFFFFF));
 #define AWQ_OE_GEN(DT)                                                                                          \
     hipLaunchKernelGGL((outerr_generic_kernel<DT>), dim3(grid), dim3(256), 0, st, w, qwp, qzp, scales, col_scale, x, \
                        N, K, T, x_row_stride, group_size, bits, tts, tiles, ref_sq ? 1 : 0, wk, err)

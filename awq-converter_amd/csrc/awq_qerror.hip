@@ -385,7 +385,7 @@ extern "C" int awq_quant_error(const void* w, int dtype, int64_t rows, int64_t K
         else { AWQ_QE_FMT(FmtF32) }
 #undef AWQ_QE_FMT
     } else {
-        const unsigned grid = (unsigned)std::min<int64_t>((ng + 3) / 4, (int64_t)256 * 64);
+        const unsigned grid = diag_cap((unsigned)std::min<int64_t>((ng + 3) / 4, (int64_t)256 * 64));
 #define AWQ_QE_GEN(DT)                                                                                         \
     hipLaunchKernelGGL((qerror_group_kernel<DT>), dim3(grid), dim3(256), 0, st, w, qwp, qzp, scales, K, group_size, \
                        G, bits, ng, group_stats, group_nonfinite)
