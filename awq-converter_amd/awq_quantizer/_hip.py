@@ -138,6 +138,10 @@ SIGNATURES = {
     "awq_quantize_groups_scaled": (_I32, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "awq_quantize_clip_scaled": (_I32, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P,
                                         _P, _P, _I64, _P]),
+    "awq_quantize_clip_output_work_bytes": (_I64, [_I64, _I64, _I64, _I64, _I32]),
+    "awq_quantize_clip_output_fast": (_I32, [_P, _I32, _I64, _I64, _P, _P, _P, _I64]),
+    "awq_quantize_clip_output": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _I32, _P, _P, _P, _I64, _I64, _I32, _I32,
+                                        _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "awq_act_recip_table": (_I32, [_P, _I32, _I64, _P, _P]),
     "awq_act_search_losses": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
     "awq_act_search_select": (_I32, [_P, _I32, _I64, _P, _I64, _P, _P, _P, _P, _P]),
@@ -729,6 +733,53 @@ def quantize_clip_scaled(w: torch.Tensor, s: torch.Tensor, x_sq: torch.Tensor, L
                                                   ptr(s), ptr(rscale), ptr(x_sq), n_grid, n_candidates, ptr(qweight),
                                                   ptr(qzeros), ptr(scales), ptr(best_idx), loss_ptr, stride,
                                                   _stream(w)), "awq_quantize_clip_scaled")
+
+
+def quantize_clip_output(w: torch.Tensor, s: torch.Tensor, x: torch.Tensor, L: int, bits: int, symmetric: bool,
+                         n_grid: int, n_candidates: int, *, cand_begin: int = 0, rscale: Optional[torch.Tensor] = None,
+                         qweight=None, qzeros=None, scales=None, best_idx=None,
+                         group_loss: Optional[torch.Tensor] = None, cand_loss: Optional[torch.Tensor] = None,
+                         loss_offset: int = 0) -> None:
+    """Clip search with the token-sample loss + packed RTN of w * diag(s) with each group's winning
+    range (awq_quantize_clip_output).  w [rows, K] device, contiguous; s fp32 [K]; x [tokens, K] of
+    w's dtype (unit column stride: a row-strided view is taken as it is); rscale as in
+    quantize_clip_scaled.  Candidates cand_begin .. cand_begin + n_candidates - 1 of n_grid.
+    group_loss fp32 [2, stride] and cand_loss fp32 [n_candidates, stride] (one stride): this weight's
+    groups are written at columns [loss_offset, loss_offset + rows * G)."""
+    if w.dim() != 2 or not w.is_contiguous():
+        raise ValueError("awq_quantize_clip_output takes a contiguous 2-D weight")
+    rows, K = w.shape
+    if x.dim() != 2 or x.shape[1] != K or x.dtype != w.dtype or x.device != w.device or (K > 1 and x.stride(1) != 1):
+        raise ValueError(f"awq_quantize_clip_output: samples must be [tokens, {K}] {w.dtype} on {w.device} with "
+                         f"contiguous rows, got {tuple(x.shape)} {x.dtype} strides {x.stride()}")
+    T = x.shape[0]
+    xs = x.stride(0) if T > 1 else max(x.stride(0), K)
+    stride, ptrs = 0, []
+    for t, n_rows, what in ((group_loss, 2, "group_loss"), (cand_loss, n_candidates, "cand_loss")):
+        if t is None:
+            ptrs.append(None)
+            continue
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != n_rows or not t.is_contiguous() \
+                or (stride and t.shape[1] != stride) or loss_offset < 0 or loss_offset + rows * (K // L) > t.shape[1]:
+            raise ValueError(f"{what} must be a contiguous fp32 [{n_rows}, stride] holding this weight's groups at "
+                             f"loss_offset (group_loss and cand_loss share the stride)")
+        stride = t.shape[1]
+        ptrs.append(ctypes.c_void_p(t.data_ptr() + 4 * loss_offset))
+    check(load_library().awq_quantize_clip_output(ptr(w), AWQ_DTYPE[w.dtype], rows, K, L, bits, int(bool(symmetric)),
+                                                  ptr(s), ptr(rscale), ptr(x), T, xs, int(n_grid), int(cand_begin),
+                                                  int(n_candidates), ptr(qweight), ptr(qzeros), ptr(scales),
+                                                  ptr(best_idx), ptrs[0], ptrs[1], stride, None, _stream(w)),
+          "awq_quantize_clip_output")
+
+
+def clip_output_fast(w: torch.Tensor, s: torch.Tensor, x: torch.Tensor, L: int,
+                     rscale: Optional[torch.Tensor] = None) -> bool:
+    """quantize_clip_output(w, s, x, L, ...) takes the MFMA kernel (awq_quantize_clip_output_fast: the
+    entry's own predicate)."""
+    K = w.shape[1]
+    xs = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), K)
+    return bool(load_library().awq_quantize_clip_output_fast(ptr(w), AWQ_DTYPE[w.dtype], K, L, ptr(s), ptr(rscale),
+                                                             ptr(x), xs))
 
 
 def apply_input_scale(w: torch.Tensor, s: torch.Tensor) -> torch.Tensor:

@@ -26,9 +26,11 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
     regular path (RTN).  A block that fails is copied unquantized (modules_to_not_convert) with its
     norms and biases left unfolded.  Writes model.safetensors (folded norm weights and biases in
     place of the source's), the configs, and awq_scales.safetensors: every block's "scales".
-    act_samples (--search_loss output): "<block prefix>.<group>.samples" -> token samples; each
-    block's four tensors go to quantize_block with loss="output"."""
+    act_samples (--search_loss output, --clip_loss output): "<block prefix>.<group>.samples" -> token
+    samples; each block's four tensors go to quantize_block, with loss="output" and / or
+    clip_loss="output"."""
     from safetensors.torch import save_file
+    from .quantization.act_search import quantize_block
     from .quantization.block_plan import plan_blocks
     by_name = {i.name: i for i in index}
     plan = plan_blocks({i.name: i.shape for i in index}, model_type_of(loader), args.group_size)
@@ -40,7 +42,8 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
         logger.error(f"Quantization on {device} failed: {e}")
         return 1
     clip_kw = {"clip": True, **cfg.act_clip} if cfg.act_clip else {}
-    output_loss = act_samples is not None
+    output_loss = act_samples is not None and args.search_loss == "output"
+    output_clip = act_samples is not None and bool(cfg.act_clip) and args.clip_loss == "output"
     results: Dict[str, Dict[str, torch.Tensor]] = {}
     overrides: Dict[str, torch.Tensor] = {}
     sidecar: Dict[str, torch.Tensor] = {}
@@ -66,11 +69,15 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
             try:
                 tensors = {n: f.result() for n, f in futs.pop(k).items()}
                 loss_kw = {}
-                if output_loss:
+                if output_loss or output_clip:
                     smp = {g: act_samples[f"{block.prefix}.{g}.samples"] for g in block.groups
                            if f"{block.prefix}.{g}.samples" in act_samples}
-                    loss_kw = {"loss": "output", "samples": smp}
-                out = quantizer.quantize_block(tensors, cfg.act_stats, block, **clip_kw, **loss_kw)
+                    loss_kw = {"samples": smp, **({"loss": "output"} if output_loss else {})}
+                if output_clip:     # (the method's signature has no clip_loss: the function behind it takes it)
+                    out = quantize_block(quantizer, tensors, cfg.act_stats, block, **clip_kw, **loss_kw,
+                                         clip_loss="output")
+                else:
+                    out = quantizer.quantize_block(tensors, cfg.act_stats, block, **clip_kw, **loss_kw)
                 exported = {n: _to_cpu(quantizer.export_autoawq(r)) for n, r in out["results"].items()}
                 host_folded = _to_cpu(out["folded"])
                 host_scales = _to_cpu(out["scales"])
@@ -83,6 +90,9 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
             logger.info(f"Successfully quantized block: {block.prefix} on {device} (folded groups: "
                         f"{[n for n, g in out['groups'].items() if g['folded']]})")
             for gname, g in out["groups"].items():
+                if g.get("clip"):
+                    logger.info(f"{block.prefix}.{gname}: clip loss {g['clip'].get('loss', 'diag')}, "
+                                f"{g['clip']['loss_before']:.6g} -> {g['clip']['loss_after']:.6g}")
                 if g.get("loss"):
                     logger.info(f"{block.prefix}.{gname}: search loss {g['loss']}, winner {g['best']}/"
                                 f"{args.search_grid} (diagonal loss: {g['diag_best']}/{args.search_grid})")

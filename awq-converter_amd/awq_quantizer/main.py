@@ -50,7 +50,7 @@ from .stream import device_name, start_warmup
 from .model_loading import TensorInfo, load_model_from_hub
 from .quantization.linear_weights import CONV1D_MODEL_TYPES, is_linear_weight
 from .utils.logger import get_logger
-from .options import AUTOAWQ_NEEDS_4_BITS, act_clip_of, check_args, check_flags, parse_args
+from .options import AUTOAWQ_NEEDS_4_BITS, act_clip_of, check_args, check_flags, parse_args, wants_samples
 from .output import ChunkWriter, _NullSink, finish_run, model_type_of, save_autoawq, writer_threads
 from .pipeline import STREAM_OPTS, TIMINGS, StreamSettings, _device_worker, new_quantizer
 # names that callers outside the package import from here
@@ -321,8 +321,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             return 1
 
         act_stats = None
-        act_samples = None      # --search_loss output: "<block>.<group>.samples" -> [tokens, in]
-        if args.search_loss == "output":
+        act_samples = None      # --search_loss / --clip_loss output: "<block>.<group>.samples" -> [tokens, in]
+        if wants_samples(args):     # loaded (or collected) once, shared by both searches
             act_samples = {}
             if args.act_samples:
                 from safetensors.torch import load_file
@@ -330,7 +330,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                 logger.info(f"Loaded token samples of {len(act_samples)} inputs from {args.act_samples}")
         if args.calib_ids:
             act_stats = calibrate_for_main(args, devices[0], logger,
-                                           samples_out=act_samples if args.search_loss == "output" else None)
+                                           samples_out=act_samples if wants_samples(args) else None)
             if act_stats is None:
                 return 1
         elif args.act_stats:

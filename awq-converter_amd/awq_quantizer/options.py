@@ -48,9 +48,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "statistics; output: the layer group's output error on token samples (--act_samples, or "
                         "collected by the --calib_ids forward)")
     p.add_argument("--act_samples", type=str, default=None,
-                   help="--search_loss output: token samples written by awq_quantizer.calibrate --samples_output")
+                   help="--search_loss output / --clip_loss output: token samples written by awq_quantizer.calibrate "
+                        "--samples_output")
     p.add_argument("--n_sample_tokens", type=int, default=512,
-                   help="--search_loss output with --calib_ids: token rows kept per linear input")
+                   help="--search_loss output / --clip_loss output with --calib_ids: token rows kept per linear input")
+    p.add_argument("--clip_loss", type=str, default="diag", choices=["diag", "output"],
+                   help="--act_clip with --fold_scales: how the clip search scores a shrink. diag: the diagonal loss "
+                        "from the statistics; output: the error at the linear's output on token samples "
+                        "(--act_samples, or collected by the --calib_ids forward), the published objective")
     p.add_argument("--clip_grid", type=int, default=20, help="--act_clip: grid size of the range shrinks")
     p.add_argument("--clip_max_shrink", type=float, default=0.5,
                    help="--act_clip: largest shrink of the group range tried")
@@ -93,6 +98,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     return build_parser().parse_args(argv)
 
 
+def wants_samples(args) -> bool:
+    """A search of this run scores its candidates on token samples."""
+    return args.search_loss == "output" or args.clip_loss == "output"
+
+
 def has_stats(args) -> bool:
     """Activation statistics come with this run, from a file or from a calibration forward."""
     return bool(args.act_stats or args.calib_ids)
@@ -124,7 +134,19 @@ def check_flags(args) -> Optional[str]:
                     "--samples_output), or --calib_ids")
         if args.calib_ids and args.n_sample_tokens <= 0:
             return "--n_sample_tokens must be positive"
-    elif args.act_samples:
+    if args.clip_loss == "output":
+        if not args.act_clip:
+            return "--clip_loss output needs --act_clip"
+        if not args.fold_scales:
+            return "--clip_loss output needs --fold_scales (and so --scale_method awq and --output_format autoawq)"
+        if args.act_samples and args.calib_ids:
+            return "--act_samples and --calib_ids both give token samples: the samples come from one of them"
+        if not args.act_samples and not args.calib_ids:
+            return ("--clip_loss output needs token samples: --act_samples FILE (awq_quantizer.calibrate "
+                    "--samples_output), or --calib_ids")
+        if args.calib_ids and args.n_sample_tokens <= 0:
+            return "--n_sample_tokens must be positive"
+    if args.act_samples and not wants_samples(args):
         return "--act_samples is read by --search_loss output"
     return None
 

@@ -90,12 +90,18 @@ def search_layer_group(weights: Dict[str, torch.Tensor], device: torch.device, *
             "input_scale": s_best, "weights": dict(zip(weights, ws)), "scaled": scaled}
 
 
-def _check_args(q, what: str, loss: str) -> None:
-    """What quantize_layer_group and quantize_block refuse first."""
+def _check_args(q, what: str, loss: str, clip_loss: Optional[str] = None) -> str:
+    """What quantize_layer_group and quantize_block refuse first.  -> the clip loss: the argument,
+    or, when it is None, the quantizer's clip_loss attribute (AWQQuantizer's methods pass None)."""
     if q.scale_method != "awq":
         raise ValueError(f"{what} needs scale_method='awq'")
     if loss not in ("diag", "output"):
         raise ValueError(f"loss must be 'diag' or 'output': {loss!r}")
+    if clip_loss is None:
+        clip_loss = getattr(q, "clip_loss", "diag")
+    if clip_loss not in ("diag", "output"):
+        raise ValueError(f"clip_loss must be 'diag' or 'output': {clip_loss!r}")
+    return clip_loss
 
 
 def _quantize_scaled(q, w: torch.Tensor, s: torch.Tensor, one_pass: bool, out: Optional[dict] = None,
@@ -116,13 +122,23 @@ def quantize_layer_group(q, weights: Dict[str, torch.Tensor], activations: Optio
                          *, x_mean: Optional[torch.Tensor] = None, x_sq: Optional[torch.Tensor] = None,
                          packed: bool = True, table: Optional[torch.Tensor] = None, clip: bool = False,
                          clip_grid: int = 20, clip_max_shrink: float = 0.5, loss: str = "diag",
-                         samples: Optional[torch.Tensor] = None) -> dict:
-    """The search over one layer group, then its weights quantized as W * diag(input_scale)."""
-    _check_args(q, "quantize_layer_group", loss)
+                         samples: Optional[torch.Tensor] = None, clip_loss: Optional[str] = None) -> dict:
+    """The search over one layer group, then its weights quantized as W * diag(input_scale).
+    clip_loss (with clip=True): "diag", the clip search's x_sq-weighted loss
+    (awq_quantize_clip_scaled), or "output", every shrink of every group scored by the error at the
+    linear's output on the token samples (awq_quantize_clip_output; samples=, default
+    `activations`); None: the quantizer's clip_loss attribute.  The "clip" dict of an "output" run
+    has the same keys plus "loss": "output", its losses are output-space losses."""
+    clip_loss = _check_args(q, "quantize_layer_group", loss, clip_loss)
     if loss == "output":
         samples = activations if samples is None else samples
         if samples is None:
             raise ValueError("loss='output' needs token samples (samples=, or activations=)")
+    clip_samples = None
+    if clip and clip_loss == "output":
+        clip_samples = activations if samples is None else samples
+        if clip_samples is None:
+            raise ValueError("clip_loss='output' needs token samples (samples=, or activations=)")
     n_clip = 0
     if clip:
         if not packed:
@@ -146,7 +162,7 @@ def quantize_layer_group(q, weights: Dict[str, torch.Tensor], activations: Optio
         sr = output_search(q, sr, samples)
         extra = {"loss": "output", "diag_losses": sr["diag_losses"], "diag_best": int(sr["diag_best"].item())}
     if clip:
-        return dict(clip_layer_group(q, weights, sr, clip_grid, n_clip), **extra)
+        return dict(clip_layer_group(q, weights, sr, clip_grid, n_clip, samples=clip_samples), **extra)
     results, s, scaled = {}, sr["input_scale"], sr["scaled"] or {}
     for name in weights:
         w = sr["weights"][name]
@@ -193,13 +209,21 @@ def output_search(q, sr: dict, samples: torch.Tensor) -> dict:
                 diag_losses=sr["losses"], diag_best=sr["best"])
 
 
-def clip_layer_group(q, weights, sr: dict, clip_grid: int, n_clip: int) -> dict:
+def clip_layer_group(q, weights, sr: dict, clip_grid: int, n_clip: int,
+                     samples: Optional[torch.Tensor] = None) -> dict:
     """quantize_layer_group's last step with clip=True: every weight through
-    awq_quantize_clip_scaled with the search's input scale, its reciprocals and x_sq; the
-    groups' losses of all weights meet in one [2, total groups] buffer, summed in fp64 by
-    awq_act_search_select (before = candidate 0, after = the winners)."""
+    awq_quantize_clip_scaled with the search's input scale, its reciprocals and x_sq — or, with
+    token samples (clip_loss="output"), through awq_quantize_clip_output with the samples in
+    x_sq's place; the groups' losses of all weights meet in one [2, total groups] buffer, summed
+    in fp64 by awq_act_search_select (before = candidate 0, after = the winners)."""
     s, x_sq = sr["input_scale"], sr["x_sq"]
     K = s.numel()
+    xs = None
+    if samples is not None:
+        if samples.dim() != 2 or samples.shape[1] != K:
+            raise ValueError(f"samples must be [tokens, {K}], got {tuple(samples.shape)}")
+        xs = device_input(samples.detach().to(next(iter(sr["weights"].values())).dtype), s.device)
+    how = "diag" if xs is None else "output"
     G = K // q.group_size
     rs = _hip.act_recip_table(s.reshape(1, K)).reshape(K)
     names = list(weights)
@@ -210,9 +234,14 @@ def clip_layer_group(q, weights, sr: dict, clip_grid: int, n_clip: int) -> dict:
         w = sr["weights"][name]
         r = q._packed_outputs(w)
         idx[name] = torch.empty(cnt, dtype=torch.int32, device=s.device)
-        _hip.quantize_clip_scaled(w, s, x_sq, q.group_size, q.bits, q.symmetric, clip_grid, n_clip,
-                                  rscale=rs, qweight=r["qweight"], qzeros=r["qzeros"], scales=r["scales"],
-                                  best_idx=idx[name], group_loss=loss, loss_offset=off)
+        if xs is None:
+            _hip.quantize_clip_scaled(w, s, x_sq, q.group_size, q.bits, q.symmetric, clip_grid, n_clip,
+                                      rscale=rs, qweight=r["qweight"], qzeros=r["qzeros"], scales=r["scales"],
+                                      best_idx=idx[name], group_loss=loss, loss_offset=off)
+        else:
+            _hip.quantize_clip_output(w, s, xs, q.group_size, q.bits, q.symmetric, clip_grid, n_clip,
+                                      rscale=rs, qweight=r["qweight"], qzeros=r["qzeros"], scales=r["scales"],
+                                      best_idx=idx[name], group_loss=loss, loss_offset=off)
         r["input_scale"] = s
         results[name] = r
         off += cnt
@@ -226,23 +255,28 @@ def clip_layer_group(q, weights, sr: dict, clip_grid: int, n_clip: int) -> dict:
         one = one.cpu()
         nz = int((idx[name] != 0).sum().item())
         per[name] = {"loss_before": float(one[0]), "loss_after": float(one[1]), "clipped_fraction": nz / cnt}
-        q.logger.info(f"awq clip {name}: clipped {nz / cnt:.1%} of {cnt} groups, loss "
+        q.logger.info(f"awq clip {name}: clipped {nz / cnt:.1%} of {cnt} groups, {how} loss "
                          f"{float(one[0]):.6g} -> {float(one[1]):.6g}")
         clipped += nz
         off += cnt
     best = int(sr["best"].item())
     q.logger.info(f"awq search over {names}: ratio {best}/{q.search_grid}, clip {n_clip}/{clip_grid}")
+    clip = {"loss_before": float(total[0]), "loss_after": float(total[1]),
+            "clipped_fraction": clipped / sum(counts), "per_weight": per, "best_idx": idx}
+    if xs is not None:
+        clip["loss"] = "output"
     return {"results": results, "input_scale": s, "best": best, "ratio": best / q.search_grid,
-            "losses": sr["losses"], "table": sr["table"],
-            "clip": {"loss_before": float(total[0]), "loss_after": float(total[1]),
-                     "clipped_fraction": clipped / sum(counts), "per_weight": per, "best_idx": idx}}
+            "losses": sr["losses"], "table": sr["table"], "clip": clip}
 
 
 def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
                    block, *, clip: bool = False, clip_grid: int = 20, clip_max_shrink: float = 0.5,
-                   samples: Optional[Dict[str, torch.Tensor]] = None, loss: str = "diag") -> dict:
-    """One decoder block: the out groups, their row folds, the in groups, their norm folds."""
-    _check_args(q, "quantize_block", loss)
+                   samples: Optional[Dict[str, torch.Tensor]] = None, loss: str = "diag",
+                   clip_loss: Optional[str] = None) -> dict:
+    """One decoder block: the out groups, their row folds, the in groups, their norm folds.
+    clip_loss="output" (with clip=True): every group with token samples takes the output-space clip
+    loss, folded or not; a group without samples the diagonal one, with a warning."""
+    clip_loss = _check_args(q, "quantize_block", loss, clip_loss)
     q._check_mode()
     dev = q.compute_device()
     clip_kw = {"clip": True, "clip_grid": clip_grid, "clip_max_shrink": clip_max_shrink} if clip else {}
@@ -281,13 +315,25 @@ def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[t
                     q.logger.warning(f"{g.name}: no token samples for loss='output': diagonal loss")
                 else:
                     loss_kw = {"loss": "output", "samples": smp}
-            out = q.quantize_layer_group(weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw, **loss_kw)
+            how = "diag"
+            if clip and clip_loss == "output":
+                smp = (samples or {}).get(g.name)
+                if smp is None:
+                    q.logger.warning(f"{g.name}: no token samples for clip_loss='output': diagonal loss")
+                else:
+                    how = "output"
+                    loss_kw["samples"] = smp
+            if how == getattr(q, "clip_loss", "diag"):    # the method resolves to the same choice: the call as it
+                out = q.quantize_layer_group(weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw, **loss_kw)
+            else:                                         # was (an override of the method is honoured)
+                out = quantize_layer_group(q, weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw, **loss_kw,
+                                           clip_loss=how)
             for m, r in out["results"].items():
                 results[m] = {k: v for k, v in r.items() if k != "input_scale"}
             s = out["input_scale"]
             report[g.name] = {"ratio": out["ratio"] if fold else None, "losses": out["losses"] if fold else None,
                               "folded": fold, "clip": out.get("clip")}
-            if loss_kw:
+            if loss_kw.get("loss"):
                 report[g.name].update(loss="output", best=out["best"], diag_best=out["diag_best"])
         else:
             for m, w in weights.items():

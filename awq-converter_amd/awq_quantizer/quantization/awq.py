@@ -44,6 +44,13 @@ class AWQQuantizer:
     AWQ Quantizer (group-wise min/max RTN quantization, HIP backend).
     """
 
+    # quantize_layer_group / quantize_block with clip=True: how the clip search scores a shrink.
+    # "diag": the x_sq-weighted loss (awq_quantize_clip_scaled); "output": the error at the
+    # linear's output on token samples (awq_quantize_clip_output), which needs samples= (or
+    # activations=).  A setting of the quantizer, like search_grid: set it on the instance.
+    # act_search.quantize_layer_group / quantize_block also take it per call (clip_loss=).
+    clip_loss = "diag"
+
     def __init__(
         self,
         bits: int = 4,

@@ -42,33 +42,6 @@ struct RedWave {
     __device__ static float sum(float v) { return wave_sum(v); }
 };
 
-// 8 values of dtype D (as fp32) -> the raw chunk the range / quantize helpers read
-template <typename F>
-__device__ __forceinline__ Chunk<F::NW> make_chunk(const float (&y)[8]) {
-    uint32_t b[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        if constexpr (F::NW == 2) b[i] = __float_as_uint(y[i]);
-        else if constexpr (std::is_same<F, FmtF16>::value) b[i] = __builtin_bit_cast(uint16_t, (_Float16)y[i]);
-        else b[i] = __float_as_uint(y[i]) >> 16;
-    }
-    Chunk<F::NW> c;
-    if constexpr (F::NW == 2) {
-        c.w[0] = u4{b[0], b[1], b[2], b[3]};
-        c.w[1] = u4{b[4], b[5], b[6], b[7]};
-    } else {
-        c.w[0] = u4{b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16)};
-    }
-    return c;
-}
-
-// awq_fast.hip's candidate arithmetic: RN_D(RN_f32(v alpha)), alpha_i = RN_f32((n_grid - i) / n_grid)
-template <typename F>
-__device__ __forceinline__ float clip_shrink(float v, float al) {
-    return F::rn(opaque(v * al));
-}
-__device__ __forceinline__ float clip_alpha(int n_grid, int i) { return (float)(n_grid - i) / (float)n_grid; }
-
 // One candidate's loss over this lane's chunk: q (awq.py:245-248) of w', dq = fp16(fp16(q - z) *
 // fp16(scale)) (awq.py:459-539), d = RN_f32(dq / s[k]) - w, c = x_sq[k] (d d), summed in element
 // order from +0.  MQ: the quotient through the reciprocals, else the IEEE division.
@@ -186,14 +159,6 @@ __device__ __forceinline__ ClipResult clip_group(const float (&w)[8], const floa
     }
     o.word = word;
     return o;
-}
-
-// a group's qzeros field (q - qmin) & mask; NaN zero points as INT32_MIN (include/awq_hip.h)
-template <int BITS, bool SYM>
-__device__ __forceinline__ uint32_t zero_field(float z) {
-    constexpr int QMIN = SYM ? -(1 << (BITS - 1)) : 0;
-    const uint32_t zn = __builtin_isnan(z) ? (uint32_t)(0u - (uint32_t)QMIN) : (uint32_t)((int)z - QMIN);
-    return zn & ((1u << BITS) - 1u);
 }
 
 struct ClipArgs {

@@ -23,8 +23,8 @@ typedef struct awq_tuning {
     int32_t max_blocks;      /* > 0: cap the grid of every launch whose kernel walks its work in a grid-stride
                                 loop (awq_internal.h diag_cap; the table in DESIGN.md): the streaming kernel
                                 (waves then walk many tiles), the loss, group-absmax, input-scale, fold,
-                                quant-error group, generic, apply / pack / dequantize and output-error
-                                kernels — so tests reach the loops' later trips at small shapes */
+                                quant-error group, generic, apply / pack / dequantize, output-error and
+                                clip-output kernels — so tests reach the loops' later trips at small shapes */
     int32_t tiles_per_wave;  /* > 1: tiles per wave of the streaming kernel's non-persistent grid */
     int32_t no_rowgroup;     /* 1: shapes of the row-segment kernel take the generic kernel */
     int32_t rg_waves;        /* 1 or 2: waves per row-segment tile (0 = cost model) */

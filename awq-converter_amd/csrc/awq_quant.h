@@ -536,6 +536,67 @@ __device__ __forceinline__ void quant8_special(const Chunk<F::NW>& v, float z, f
     }
 }
 
+// ---- the clip searches with a column scale (awq_actclip.hip, awq_clipout.hip) ----
+// 8 values of dtype D (as fp32) -> the raw chunk the range / quantize helpers read
+template <typename F>
+__device__ __forceinline__ Chunk<F::NW> make_chunk(const float (&y)[8]) {
+    uint32_t b[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if constexpr (F::NW == 2) b[i] = __float_as_uint(y[i]);
+        else if constexpr (std::is_same<F, FmtF16>::value) b[i] = __builtin_bit_cast(uint16_t, (_Float16)y[i]);
+        else b[i] = __float_as_uint(y[i]) >> 16;
+    }
+    Chunk<F::NW> c;
+    if constexpr (F::NW == 2) {
+        c.w[0] = u4{b[0], b[1], b[2], b[3]};
+        c.w[1] = u4{b[4], b[5], b[6], b[7]};
+    } else {
+        c.w[0] = u4{b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16)};
+    }
+    return c;
+}
+
+// awq_fast.hip's candidate arithmetic: RN_D(RN_f32(v alpha)), alpha_i = RN_f32((n_grid - i) / n_grid)
+template <typename F>
+__device__ __forceinline__ float clip_shrink(float v, float al) {
+    return F::rn(opaque(v * al));
+}
+__device__ __forceinline__ float clip_alpha(int n_grid, int i) { return (float)(n_grid - i) / (float)n_grid; }
+
+// RTN of a lane's 8 values of w' with the winner's parameters (awq_fast.hip compute_tile step 4).
+// User: awq_clipout.hip.  Same bits, different code: awq_actclip.hip's clip_group ends with these
+// lines written out — calling this function there moves its register allocation (scripts/isa_diff.py),
+// and its generated code is measured.
+template <typename F, int BITS, bool SYM>
+__device__ __forceinline__ u2v pack_winner(const Chunk<F::NW>& v, const GroupParams& p) {
+    const float zj = SYM ? 0.0f : p.z;
+    u2v word = quant8_fast<F, BITS, SYM, false>(v, p.r, zj, p.s);
+    if (__builtin_expect(!F::fast(p.r), 0)) {
+        uint32_t nib[8];
+        int32_t qs[8];
+        quant8_special<F, BITS, SYM>(v, zj, p.s, nib, qs);
+        if (BITS == 4) {
+            uint32_t acc = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc |= nib[i] << (4 * i);
+            word.x = acc;
+        } else {
+            word.x = nib[0] | (nib[1] << 8) | (nib[2] << 16) | (nib[3] << 24);
+            word.y = nib[4] | (nib[5] << 8) | (nib[6] << 16) | (nib[7] << 24);
+        }
+    }
+    return word;
+}
+
+// a group's qzeros field (q - qmin) & mask; NaN zero points as INT32_MIN (include/awq_hip.h)
+template <int BITS, bool SYM>
+__device__ __forceinline__ uint32_t zero_field(float z) {
+    constexpr int QMIN = SYM ? -(1 << (BITS - 1)) : 0;
+    const uint32_t zn = __builtin_isnan(z) ? (uint32_t)(0u - (uint32_t)QMIN) : (uint32_t)((int)z - QMIN);
+    return zn & ((1u << BITS) - 1u);
+}
+
 // fp16 bits of a group's scale (awq.py:411); NaN scales per nan_scale_code (awq_internal.h):
 // gnan = the group holds a NaN (else the NaN came from inf - inf)
 __device__ __forceinline__ uint16_t f16_bits(float s, bool gnan, uint32_t nan_code) {

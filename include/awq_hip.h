@@ -658,6 +658,60 @@ int awq_quantize_clip_scaled(const void* w, int dtype, int64_t rows, int64_t K, 
                              int n_grid, int n_candidates, int32_t* qweight, int32_t* qzeros, uint16_t* scales,
                              int32_t* best_idx, float* group_loss, int64_t loss_stride, void* stream);
 
+/* ---- Clip search with the token-sample loss (additive to ABI 17): awq_quantize_clip_scaled's
+ * candidates scored by the published objective (AutoAWQ _compute_best_clip), the error at the
+ * linear's output on calibration samples x [T, K] (dtype D of w, row stride x_row_stride >= K
+ * elements: the unscaled samples, as awq_output_error takes them).  Every step reuses arithmetic
+ * pinned above:
+ *   w', each group's [mn, mx], alpha_i, the shrunk range, its scale and zero point, q and dq:
+ *       awq_quantize_clip_scaled's, for the candidates cand_begin <= i < cand_begin + n_candidates
+ *       <= n_grid.  Hence, for the same i, a group's packed bits are those
+ *       awq_quantize_clip_scaled writes.
+ *   d = RN_f32(RN_f32(dq / s[k]) - fp32(w)), against the ORIGINAL w, no contraction
+ *       (awq_output_error's d with col_scale = s); col_rscale as in awq_quantize_clip_scaled: the
+ *       same bits as the IEEE division.
+ *   loss of (row n, group g, candidate i): E[t] = sum_{k in g} d[n, k] x[t, k], loss = sum_t E[t]^2.
+ * Accuracy: the order of the sum over k is the implementation's, so the contract is awq_output_error's
+ * bound with the group size L for K: |E - E_exact| <= eps_L * sum_{k in g} |d| |x|, eps_L = 2^-17 +
+ * L 2^-22 (L 2^-22 alone where the operands are f32: the generic kernel); the sum over t adds at most
+ * (T + 1) 2^-24 relative.  No floating-point atomics: a (row, group, candidate) loss is formed in one
+ * place, the tokens in a fixed order — the same bits from run to run.
+ * Winner: the first strict minimum OF THE fp32 LOSSES AS RETURNED; a NaN loss never wins; NaN / inf
+ * groups and ties keep the first candidate (cand_begin).
+ * Outputs (each may be NULL, at least one must be given):
+ *   qweight / qzeros / scales: RTN of w' with the winner's range (qzeros is zeroed on the stream
+ *       first, then every group ORs its field in);
+ *   best_idx int32 [rows * G]: the winners' absolute candidate indices;
+ *   group_loss fp32 [2, loss_stride]: row 0 the loss of candidate cand_begin, row 1 the winner's —
+ *       the layout awq_act_search_select(group_loss, 2, loss_stride, ...) reads;
+ *   cand_loss fp32 [n_candidates, loss_stride]: every candidate's loss, row i - cand_begin.
+ *   This weight's groups sit at [0, rows * G) of every row; loss_stride >= rows * G.
+ * n_candidates = 1 forces candidate cand_begin for every group (cand_begin = 0:
+ * awq_quantize_groups_scaled's bits).
+ * Checked in this order, before any launch (the pointers are not looked at until the last two):
+ * bits other than 4 / 8, group_size <= 0, a negative rows / K / T: AWQ_EINVAL; a group_size that is
+ * not a power of two in [8, 512], K % group_size != 0, fp64: AWQ_EUNSUPPORTED; another dtype code,
+ * x_row_stride < K, n_grid < 1, n_candidates < 1, cand_begin < 0 or cand_begin + n_candidates >
+ * n_grid: AWQ_EINVAL; rows K, rows T or T x_row_stride above 2^60, rows G >= 2^31: AWQ_EUNSUPPORTED;
+ * no output: AWQ_EINVAL; rows == 0 or K == 0: AWQ_OK, nothing is read or written; a NULL w /
+ * col_scale (x when T > 0), a short loss_stride, a misaligned pointer: AWQ_EINVAL.
+ * T == 0: every loss is +0, every winner cand_begin.
+ * Kernels: bf16 with group_size 32 / 64 / 128 / 256, 16-B aligned w / x / col_scale / col_rscale,
+ * x_row_stride % 8 == 0 (and K, x_row_stride < 2^22): v_mfma_f32_32x32x16_bf16 on the hi / lo split
+ * of d, 128 rows of one group per workgroup; everything else: one wave per group on f32 operands.
+ * `work` is not used (awq_quantize_clip_output_work_bytes returns 0): it may be NULL. */
+int64_t awq_quantize_clip_output_work_bytes(int64_t rows, int64_t K, int64_t group_size, int64_t T, int n_candidates);
+/* 1 if a call with these arguments (already accepted by the checks above) takes the MFMA kernel, else
+ * 0: the predicate the entry itself routes by.  Host only, nothing is dereferenced. */
+int awq_quantize_clip_output_fast(const void* w, int dtype, int64_t K, int64_t group_size, const float* col_scale,
+                                  const float* col_rscale, const void* x, int64_t x_row_stride);
+int awq_quantize_clip_output(const void* w, int dtype, int64_t rows, int64_t K, int64_t group_size, int bits,
+                             int symmetric, const float* col_scale, const float* col_rscale,
+                             const void* x, int64_t T, int64_t x_row_stride,   /* samples [T, K] of `dtype` */
+                             int n_grid, int cand_begin, int n_candidates,
+                             int32_t* qweight, int32_t* qzeros, uint16_t* scales, int32_t* best_idx,
+                             float* group_loss, float* cand_loss, int64_t loss_stride, void* work, void* stream);
+
 /* ---- Scale folding (additive to ABI 17).  A searched weight is W * diag(s): it is usable only
  * once 1 / s is folded into whatever produces its input — the preceding norm's weight, or the
  * rows (and bias) of the preceding linear.  This is that fold, for rows:
