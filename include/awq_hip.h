@@ -13,7 +13,8 @@
  *     caller unless stated otherwise; the library never allocates or frees device memory
  *     and keeps no global mutable state (re-entrant; one stream per call);
  *   - `stream` is a hipStream_t (NULL = legacy default stream); launches are asynchronous
- *     on that stream, nothing synchronises;
+ *     on that stream, nothing synchronises (pinned per entry point, memsets and later stages
+ *     included, by tests/test_stream_order_gpu.py; re-entrancy by tests/test_reentrancy_host.py);
  *   - return 0 on success, an AWQ_E* code otherwise; awq_last_error() (thread-local)
  *     then holds a message.  Invalid arguments are reported before anything is launched.
  *

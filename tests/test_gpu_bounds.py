@@ -11,13 +11,17 @@ and once on its bitwise complement.  Both runs must
   3. do so with the workspaces left holding the fill.
 Expectations come from the CPU oracle, from the expectation helpers of test_gpu_qerror.py and
 test_gpu_act_clip.py, and from torch's CPU ops; each is computed once per case and shared by the
-two polarities.  Every case asserts the predicate that selects its kernel before it runs."""
+two polarities.  Every case asserts the predicate that selects its kernel before it runs.
+Inside stream_gate.ordered() (tests/test_stream_order_gpu.py) Call.run makes the same checks on a
+non-blocking stream whose memory is stale until a device-side gate has passed; outside it nothing
+changes."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
+import stream_gate
 from guard_arena import Arena
 from oracle import awq_oracle as orc
 from test_gpu_act_clip import expect_clip
@@ -52,9 +56,9 @@ def _stream(dev):
 
 # ---------------------------------------------------------------- the mechanism
 class Buf:
-    def __init__(self, name, nbytes, data, expect, skew, align, untouched, nan_dtype, written):
+    def __init__(self, name, nbytes, data, expect, skew, align, untouched, nan_dtype, written, pointers=False):
         self.name, self.nbytes, self.data, self.skew, self.align = name, nbytes, data, skew, align
-        self.untouched, self.nan_dtype, self.written = untouched, nan_dtype, written
+        self.untouched, self.nan_dtype, self.written, self.pointers = untouched, nan_dtype, written, pointers
         self.expect = None if expect is None else _bytes(expect)
         self.region = None
 
@@ -88,11 +92,14 @@ class Call:
         self.bufs.append(b)
         return b
 
-    def inp(self, name, t=None, *, nbytes=None, skew=0, align=256, untouched=True, expect=None, nan_dtype=None):
-        """An input (contents stored after every fill).  expect: the input is also an output."""
+    def inp(self, name, t=None, *, nbytes=None, skew=0, align=256, untouched=True, expect=None, nan_dtype=None,
+            pointers=False):
+        """An input (contents stored after every fill).  expect: the input is also an output.
+        pointers: the kernel turns these bytes into addresses or indices (descriptors, a block
+        table) — in ordered mode (tests/stream_gate.py) they are never stale."""
         data = None if t is None else _bytes(t)
         return self._add(Buf(name, data.numel() if nbytes is None else nbytes, data, expect, skew, align, untouched,
-                             nan_dtype, None))
+                             nan_dtype, None, pointers))
 
     def out(self, name, expect, *, skew=0, align=256, nan_dtype=None, written=None):
         """An output of exactly the expectation's size, left holding the fill.  nan_dtype: NaN
@@ -120,7 +127,8 @@ class Call:
             for b in self.bufs:
                 if b.data is not None:
                     b.region.store(b.data)
-            rc = launch()
+            gate = stream_gate.active()
+            rc = launch() if gate is None else self._ordered(gate, launch)
             if rc != 0:
                 from awq_quantizer import _hip
                 raise AssertionError(f"entry point returned {rc}: {_hip.last_error()}")
@@ -133,6 +141,22 @@ class Call:
             for b in self.bufs:                                      # 2./3. every output byte, from any contents
                 if b.expect is not None:
                     self._compare(b, pol)
+
+    def _ordered(self, gate, launch):
+        """Inside stream_gate.ordered(): the arena goes stale (the complement of what the call must
+        find, pointer-bearing inputs excepted), and the gate, the restore and the call follow on
+        the gate's stream, with stream 0 synchronised while the gate still spins."""
+        buf = self.arena.buf
+        shadow = buf.clone()
+        rc = launch()                # not the test: the runtime loads a kernel's code at its first launch
+        if rc != 0:                  # (tens of milliseconds), which must not happen behind the gate
+            return rc
+        torch.bitwise_not(shadow, out=buf)
+        for b in self.bufs:
+            if b.pointers:
+                b.region.u8.copy_(shadow[b.region.start:b.region.end])
+        torch.cuda.synchronize(self.dev)
+        return gate.behind_gate(lambda: buf.copy_(shadow), launch)
 
     def _compare(self, b, pol):
         got = b.region.u8.cpu()
@@ -345,14 +369,14 @@ def test_quantize_ragged(dtype, bits, sym, search, table):
     ob = {n: [c.out(f"{n}{i}", e[n]) for i, e in enumerate(want)]
           for n in ("qweight", "qzeros", "scales", "tensor_q", "zeros")}
     n = len(ws)
-    descs_b = c.inp("descs", nbytes=80 * n)
+    descs_b = c.inp("descs", nbytes=80 * n, pointers=True)
     # the table's length depends on the tile count alone: plan with placeholder pointers first
     plan = [_hip.TensorDesc(w=16, rows=r, K=k) for (r, k) in rk]
     total = _hip.plan_ragged(plan, bits, gs)
     arr = (_hip.TensorDesc * n)(*plan)
     tlen = lib.awq_plan_block_tensor(arr, n, total, None, 0)
     assert tlen > 0
-    table_b = c.inp("block_table", nbytes=4 * tlen) if table else None
+    table_b = c.inp("block_table", nbytes=4 * tlen, pointers=True) if table else None
     c.build()
     descs = [_hip.TensorDesc(w=wb[i].addr, rows=r, K=k, qweight=ob["qweight"][i].addr, qzeros=ob["qzeros"][i].addr,
                              scales=ob["scales"][i].addr, tensor_q=ob["tensor_q"][i].addr, zeros=ob["zeros"][i].addr)
