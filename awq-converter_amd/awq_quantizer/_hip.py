@@ -150,6 +150,7 @@ SIGNATURES = {
     "awq_act_stats_accum": (_I32, [_P, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "awq_rmsnorm_stats": (_I32, [_P, _I32, _I64, _I64, _P, ctypes.c_float, _P, _I64, _P, _P, _P, _P]),
     "awq_swiglu_stats": (_I32, [_P, _P, _I32, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P]),
+    "awq_logit_compare": (_I32, [_P, _P, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -605,6 +606,32 @@ def swiglu_stats(gate: torch.Tensor, up: torch.Tensor, tokens_before: int = 0,
     check(load_library().awq_swiglu_stats(ptr(gate), ptr(up), AWQ_DTYPE[gate.dtype], T, K, sg, ptr(out), tokens_before,
                                           ptr(work), ptr(acc_abs), ptr(acc_sq), _stream(gate)), "awq_swiglu_stats")
     return out
+
+
+# ---- evaluation tail (include/awq_hip.h awq_logit_compare) ----
+def logit_compare(ref: torch.Tensor, q: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None, *,
+                  nll_ref: Optional[torch.Tensor] = None, nll_q: Optional[torch.Tensor] = None,
+                  kl: Optional[torch.Tensor] = None, argmax_ref: Optional[torch.Tensor] = None,
+                  argmax_q: Optional[torch.Tensor] = None) -> None:
+    """awq_logit_compare on ref / q [T, V] (any row stride, one dtype; q may be None) and int64
+    targets [T] (may be None): writes the outputs that are given (fp32 [T] / int32 [T], contiguous)."""
+    sr = _rows_view(ref, "logit_compare")
+    T, V = ref.shape
+    sq = 0
+    if q is not None:
+        sq = _rows_view(q, "logit_compare")
+        if q.shape != ref.shape or q.dtype != ref.dtype or q.device != ref.device:
+            raise ValueError("logit_compare takes ref and q of one shape, dtype and device")
+    if targets is not None and (targets.dtype != torch.int64 or targets.shape != (T,) or not targets.is_contiguous()
+                                or targets.device != ref.device):
+        raise ValueError(f"logit_compare: targets must be a contiguous int64 [{T}] on {ref.device}")
+    for name, t, dt in (("nll_ref", nll_ref, torch.float32), ("nll_q", nll_q, torch.float32), ("kl", kl, torch.float32),
+                        ("argmax_ref", argmax_ref, torch.int32), ("argmax_q", argmax_q, torch.int32)):
+        if t is not None and (t.dtype != dt or t.shape != (T,) or not t.is_contiguous() or t.device != ref.device):
+            raise ValueError(f"logit_compare: {name} must be a contiguous {dt} [{T}] on {ref.device}")
+    check(load_library().awq_logit_compare(ptr(ref), ptr(q), AWQ_DTYPE[ref.dtype], T, V, sr, sq, ptr(targets),
+                                           ptr(nll_ref), ptr(nll_q), ptr(kl), ptr(argmax_ref), ptr(argmax_q),
+                                           _stream(ref)), "awq_logit_compare")
 
 
 def column_mean(acc: torch.Tensor, divisor: float) -> torch.Tensor:

@@ -179,6 +179,8 @@ class HipOps:
         return out
 
     def swiglu(self, gate: torch.Tensor, up: torch.Tensor, acc, fused: bool) -> torch.Tensor:
+        if acc is None:
+            return self._hip.swiglu_stats(gate, up)
         if fused and acc.fusable():
             out = self._hip.swiglu_stats(gate, up, acc.tokens, acc.acc_abs, acc.acc_sq)
             acc.added(gate.shape[0])
@@ -188,7 +190,8 @@ class HipOps:
         return out
 
     def accum(self, x: torch.Tensor, acc) -> None:
-        acc.add(x)
+        if acc is not None:
+            acc.add(x)
 
 
 # ---------------------------------------------------------------- the driver
@@ -220,12 +223,17 @@ def _linear_names(prefix: str, names) -> Dict[str, List[str]]:
 
 def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torch.dtype, device, ops,
                 batch_tokens: int = 8192, readers: int = 4, logger=None, n_sample_tokens: int = 0,
-                samples_out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+                samples_out: Optional[Dict[str, torch.Tensor]] = None, stats: bool = True,
+                hidden_out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
     """The block-by-block pass.  Returns weight name -> (x_mean, x_sq) (fp32, on the CPU).
     n_sample_tokens > 0 also keeps, per block and distinct input, the rows sample_rows(n * seq,
     n_sample_tokens) of the token-major activation (the tensors the producers return, compute
     dtype, gathered per micro-batch) in samples_out["<block prefix>.<group>.samples"] (CPU);
-    0 keeps nothing and changes nothing."""
+    0 keeps nothing and changes nothing.
+    stats=False takes no statistics (every accumulator handed to `ops` is None, the result is empty
+    and the final norm is left to the caller); hidden_out, when given, receives the resident hidden
+    states after the last block, before the final norm, as hidden_out["hidden"] ([n * seq, H],
+    compute dtype, on the device).  Both are for the evaluation pass (awq_quantizer.evaluation)."""
     device = torch.device(device)
     index = {i.name: i for i in loader.tensor_index()}
     root = "model." if "model.embed_tokens.weight" in index else ""
@@ -283,7 +291,8 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
                 b_gu = torch.cat([w["mlp.gate_proj.bias"], w["mlp.up_proj.bias"]])
             inter = w["mlp.gate_proj.weight"].shape[0]
             accs = {"attn_in": ops.new_acc(H), "attn_out": ops.new_acc(w["self_attn.o_proj.weight"].shape[1]),
-                    "mlp_in": ops.new_acc(H), "mlp_out": ops.new_acc(inter)}
+                    "mlp_in": ops.new_acc(H), "mlp_out": ops.new_acc(inter)} if stats else dict.fromkeys(
+                        ("attn_in", "attn_out", "mlp_in", "mlp_out"))
             kept = {g: [] for g in accs}
             for a, b in spans:
                 x = hidden[a * seq:b * seq]                       # [T, H] view of the resident states
@@ -315,12 +324,15 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
                 take("mlp_out", act)
                 x += F.linear(act, w["mlp.down_proj.weight"], w.get("mlp.down_proj.bias"))
             for group, acc in accs.items():
-                publish(acc, lin[group])
+                if acc is not None:
+                    publish(acc, lin[group])
                 if kept[group]:
                     samples_out[f"{p}.{group}.samples"] = torch.cat(kept[group]).cpu()
             if logger:
-                logger.info(f"Calibrated block: {p}")
-        if "lm_head.weight" in index:
+                logger.info(f"Calibrated block: {p}" if stats else f"Ran block: {p}")
+        if hidden_out is not None:
+            hidden_out["hidden"] = hidden
+        if stats and "lm_head.weight" in index:
             wn = dev(loader.read(index[f"{root}norm.weight"]))
             acc = ops.new_acc(H)
             for a, b in spans:

@@ -56,34 +56,9 @@ __device__ __forceinline__ uint32_t dtype_bits(float y) {   // y: a value of the
 }
 
 template <typename F>
-__device__ __forceinline__ float load1(const void* base, int64_t i) {
-    if constexpr (F::NW == 2) return ((const float*)base)[i];
-    else return F::dec(((const uint16_t*)base)[i]);
-}
-
-template <typename F>
 __device__ __forceinline__ void store1(void* base, int64_t i, float y) {
     if constexpr (F::NW == 2) ((float*)base)[i] = y;
     else ((uint16_t*)base)[i] = (uint16_t)dtype_bits<F>(y);
-}
-
-// 8 consecutive elements (16-B aligned) as fp32
-template <typename F>
-__device__ __forceinline__ void load8(const void* base, int64_t i, float (&v)[8]) {
-    if constexpr (F::NW == 2) {
-        const float4* p = (const float4*)((const float*)base + i);
-        const float4 a = p[0], b = p[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-        const uint4 u = *(const uint4*)((const uint16_t*)base + i);
-        const uint32_t h[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = F::dec(h[j] & 0xFFFFu);
-            v[2 * j + 1] = F::dec(h[j] >> 16);
-        }
-    }
 }
 
 template <typename F>

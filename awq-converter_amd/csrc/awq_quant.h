@@ -605,6 +605,33 @@ __device__ __forceinline__ uint16_t f16_bits(float s, bool gnan, uint32_t nan_co
     return __builtin_bit_cast(uint16_t, h);
 }
 
+// ---- plain element access of the row kernels (awq_calib.hip, awq_logits.hip) ----
+// one element of dtype D as fp32
+template <typename F>
+__device__ __forceinline__ float load1(const void* base, int64_t i) {
+    if constexpr (F::NW == 2) return ((const float*)base)[i];
+    else return F::dec(((const uint16_t*)base)[i]);
+}
+
+// 8 consecutive elements (16-B aligned) as fp32
+template <typename F>
+__device__ __forceinline__ void load8(const void* base, int64_t i, float (&v)[8]) {
+    if constexpr (F::NW == 2) {
+        const float4* p = (const float4*)((const float*)base + i);
+        const float4 a = p[0], b = p[1];
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        const uint4 u = *(const uint4*)((const uint16_t*)base + i);
+        const uint32_t h[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[2 * j] = F::dec(h[j] & 0xFFFFu);
+            v[2 * j + 1] = F::dec(h[j] >> 16);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // Tile context: everything a wave needs about one tile, all wave-uniform (SGPRs).
 // ---------------------------------------------------------------------------------------

@@ -782,6 +782,67 @@ int awq_rmsnorm_stats(const void* x, int dtype, int64_t tokens, int64_t H, const
 int awq_swiglu_stats(const void* gate, const void* up, int dtype, int64_t tokens, int64_t K, int64_t row_stride,
                      void* out, int64_t tokens_before, double* work, double* acc_abs, double* acc_sq, void* stream);
 
+/* ---- Logit comparison (additive to ABI 17; beyond the reference): the tail of a model-level
+ * evaluation.  ref and q are logits [T, V] of dtype D = bf16 / fp16 / fp32, each with its own row
+ * stride in elements (>= V).  Per row t, a = fp32(ref[t, .]), b = fp32(q[t, .]), m_r = max_v a_v:
+ *   S_r = sum_v exp(a_v - m_r),  lse_r = m_r + log S_r           (S_q, lse_q likewise from b)
+ *   nll_ref[t] = lse_r - a[targets[t]],  nll_q[t] = lse_q - b[targets[t]]
+ *       targets[t] < 0: not scored, both +0;  targets[t] >= V: both NaN
+ *   kl[t] = (A / S_r - lse_r) + lse_q,  A = sum_v exp(a_v - m_r) (a_v - b_v)
+ *       = KL(softmax a || softmax b), as computed: no clamp, it may be negative within the bound below
+ *   argmax_ref[t], argmax_q[t] = the LOWEST index attaining the row's maximum
+ * A row of ref that holds a NaN or +-inf: nll_ref[t] = kl[t] = NaN, argmax_ref[t] = -1; a row of q
+ * likewise for nll_q, kl, argmax_q.  Nothing else is masked and no row affects another.
+ * q = NULL: the single-model form (nll_ref and argmax_ref only; q_row_stride, nll_q, kl and argmax_q
+ * are not looked at).  targets = NULL: no nll output.  Any output pointer may be NULL.
+ * lse_r and lse_q come from one instruction sequence: bit-identical rows of ref and q give
+ * nll_q == nll_ref bit for bit and kl[t] == +0.
+ *
+ * Order (fixed; the same bits from run to run, for any T, on either path; no atomics).  One
+ * 256-thread workgroup per row.  The row is cut into 8-element chunks c = 0 .. ceil(V/8)-1; thread
+ * i takes chunks i, i + 256, ... ascending and keeps (m, S, A), starting from (-inf, +0, +0).  Per
+ * chunk: cm = the chunk's maximum; if cm > m: e = expf(m - cm), m = cm, else e = 1;
+ * w_j = expf(x_j - m); S = S e + (((0 + w_0) + w_1) + ... + w_7); A = A e + (((0 + w_0 d_0) + ...) +
+ * w_7 d_7), d_j = a_j - b_j (elements past V add +0).  Then M = the maximum of the threads' m;
+ * thread i contributes S f, A f with f = 1 if its m == M, else expf(m - M); the 256 contributions
+ * are added as the pairwise tree over the 64 threads of each wave, adjacent pairs first
+ * (awq_quantize_search's tree), then (w0 + w1) + (w2 + w3) over the four waves.  lse = M + logf(S).
+ * One online pass: each matrix is read once.
+ *
+ * Error contract (fp64 evaluation of the definitions on the same inputs), per scored finite row:
+ *   |nll - nll64| <= (D + C + c0) 2^-24 + 2^-23 |lse| + 2^-24 |nll|
+ *   |kl - kl64|   <= (D + C + c0) 2^-23 (1 + M1) + 3 2^-24 (M1 + |lse_r| + |lse_q|),
+ *                    M1 = sum_v p_v |a_v - b_v|, p = softmax a
+ * with
+ *   D  = 104: a term with x_v - M < -104 is flushed (e^-104 < 2^-149), one above it carries the
+ *        rounding of its exponent: the exponents x - m, m - m', ..., m'' - M of the factors a term
+ *        passes through all have one sign and add up to x_v - M, so together they are wrong by at
+ *        most 2^-24 |x_v - M| <= D 2^-24, which is the term's relative error;
+ *   C  = 4 n + 20, n = ceil(ceil(V / 8) / 256) chunks per thread: the roundings a term passes after
+ *        its own expf, in units of 2^-24 relative: <= 8 additions of the chunk sum, per later chunk
+ *        of the thread one rescale (expf <= 1 ulp = 2, the product 1) and one addition, the rescale
+ *        to M (3), 8 additions of the tree, one spare;
+ *   c0 = 48: the term's own expf (2), logf <= 1 ulp of |log S| <= 2^-23 ln 2^31 (44), and 2 for what
+ *        the flushed terms (< 2^31 2^-149 of S >= 1) and second-order products add.
+ *   The three further terms: the addition M + log S (2^-24 |lse|), its fp64 counterpart's inputs
+ *   (none) and the final subtraction, whose result is rounded to fp32: 2^-24 |nll|, |nll| <= |lse| +
+ *   |a_target| (without it no fp32 output could meet the bound when |a_target| >> |lse|).
+ *   kl: A / S_r is a p-weighted mean of d_v whose weights carry (D + C + c0) 2^-24 twice (numerator
+ *   and S_r), the two lse their bound above, the two final additions <= 2^-24 (2 M1 + 3 |lse_r| +
+ *   2 |lse_q|).  expf / logf are the device math library's (<= 1 ulp).
+ *
+ * Kernels, the same bits: 16-B aligned bases and row strides % 8 == 0 (fp32: % 4): 16-B loads, the
+ * ragged last chunk element by element; anything else: every chunk element by element.
+ * Checked in this order, nothing launched on a failure: the dtype (AWQ_EUNSUPPORTED); T < 0 or V < 1
+ * (AWQ_EINVAL); T == 0: AWQ_OK, no pointer is looked at; V >= 2^31; ref == NULL; a row stride < V;
+ * T x row stride > 2^60 (all AWQ_EINVAL).  More than 65536 rows: the grid is capped and a workgroup
+ * takes rows blockIdx, blockIdx + grid, ...  Caller-owned device memory, the caller's stream, no
+ * workspace, no allocation, no synchronisation. */
+int awq_logit_compare(const void* ref, const void* q, int dtype, int64_t T, int64_t V,
+                      int64_t ref_row_stride, int64_t q_row_stride, const int64_t* targets,
+                      float* nll_ref, float* nll_q, float* kl,
+                      int32_t* argmax_ref, int32_t* argmax_q, void* stream);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
