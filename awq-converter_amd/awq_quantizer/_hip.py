@@ -106,6 +106,8 @@ SIGNATURES = {
     "awq_dequant_ceiling": (_I32, [_P, _P, _I64, _P]),
     "awq_export_autoawq_gemm": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _P, _P, _P, _P]),
     "awq_import_autoawq_gemm": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _P, _P, _P, _P]),
+    "awq_export_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "awq_import_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
     "awq_plan_block_tensor": (_I64, [ctypes.POINTER(TensorDesc), _I32, _I64, _P, _I64]),
     "awq_ragged_flags": (_I32, [ctypes.POINTER(TensorDesc), _I32, _I64]),
     "awq_quantize_ragged": (_I32, [_P, _I32, _I64, _P, _I32, _I32, _I32, _I64, _I32, _P]),
@@ -434,6 +436,26 @@ def import_autoawq_gemm(qweight_t, qzeros_t, scales_t, N: int, K: int, L: int, b
                                                 ptr(qweight), ptr(qzeros), ptr(scales),
                                                 ctypes.c_void_p(stream_ptr(dev)))
     check(rc, "awq_import_autoawq_gemm")
+
+
+def export_gptq(qweight, qzeros, scales, N: int, K: int, L: int, bits: int, symmetric: bool, zero_offset: int,
+                qweight_t, qzeros_t, scales_t, g_idx) -> None:
+    """awq_export_gptq; an output given as None is not produced (nor its input read)."""
+    dev = next(t for t in (qweight_t, qzeros_t, scales_t, g_idx) if t is not None).device
+    rc = load_library().awq_export_gptq(ptr(qweight), ptr(qzeros), ptr(scales), N, K, L, bits, int(symmetric),
+                                        zero_offset, ptr(qweight_t), ptr(qzeros_t), ptr(scales_t), ptr(g_idx),
+                                        ctypes.c_void_p(stream_ptr(dev)))
+    check(rc, "awq_export_gptq")
+
+
+def import_gptq(qweight_t, qzeros_t, scales_t, N: int, K: int, L: int, bits: int, symmetric: bool, zero_offset: int,
+                qweight, qzeros, scales) -> None:
+    """awq_import_gptq; an output given as None is not produced (nor its input read)."""
+    dev = next(t for t in (qweight, qzeros, scales) if t is not None).device
+    rc = load_library().awq_import_gptq(ptr(qweight_t), ptr(qzeros_t), ptr(scales_t), N, K, L, bits, int(symmetric),
+                                        zero_offset, ptr(qweight), ptr(qzeros), ptr(scales),
+                                        ctypes.c_void_p(stream_ptr(dev)))
+    check(rc, "awq_import_gptq")
 
 
 def dequantize(tensor_q, scales, zeros, rows, K, L, out) -> None:

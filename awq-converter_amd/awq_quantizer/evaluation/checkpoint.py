@@ -7,11 +7,13 @@ runs the quantized model exactly as it runs the source.
       without a folded producer) is brought back to the source's domain, w^ = RN(dq / input_scale);
   autoawq (model.safetensors or its shards + quant_config.json): every qweight / qzeros / scales
       triple is dequantized, every other tensor is read as written.  A --fold_scales directory is
-      used as it stands: folded norms, biases and rows with scaled-domain weights.
+      used as it stands: folded norms, biases and rows with scaled-domain weights;
+  gptq (the same files + quantize_config.json with quant_method "gptq"): the same, every linear
+      imported through awq_import_gptq (g_idx is checked to be k // group_size and not read again).
 
 Tensors the directory does not hold come from the source.  `dequant` does the arithmetic:
 DeviceDequant runs the library's kernels (awq_dequantize, awq_dequantize_packed,
-awq_import_autoawq_gemm); host tests inject a stub.
+awq_import_autoawq_gemm, awq_import_gptq); host tests inject a stub.
 """
 from __future__ import annotations
 
@@ -22,7 +24,8 @@ from typing import Dict, List
 
 import torch
 
-from ..verify import CHUNK_STEM, _split_flat, autoawq_files, is_autoawq_dir, read_quant_config
+from ..verify import (CHUNK_STEM, _split_flat, autoawq_files, is_autoawq_dir, is_gptq_dir, read_gptq_config,
+                      read_quant_config)
 
 _GEMM_KEYS = ("qweight", "qzeros", "scales")
 
@@ -49,6 +52,11 @@ class DeviceDequant:
     def autoawq(self, gemm: Dict[str, torch.Tensor], group_size: int, symmetric: bool) -> torch.Tensor:
         return self.q.dequantize_autoawq(gemm, group_size=group_size, symmetric=symmetric)
 
+    def gptq(self, gptq: Dict[str, torch.Tensor], group_size: int, symmetric: bool,
+             checkpoint_format: str) -> torch.Tensor:
+        return self.q.dequantize_gptq(gptq, group_size=group_size, symmetric=symmetric,
+                                      checkpoint_format=checkpoint_format)
+
     def unscale(self, w: torch.Tensor, input_scale: torch.Tensor) -> torch.Tensor:
         return w.float() / input_scale.to(w.device, torch.float32)[None, :]
 
@@ -65,11 +73,13 @@ class QuantizedCheckpoint:
         self._lock = threading.Lock()         # run_decoder reads the next block ahead on a worker thread
         if is_autoawq_dir(quantized_dir):
             from safetensors import safe_open
-            self.format = "autoawq"
-            cfg, problems = read_quant_config(quantized_dir)
+            self.format = "gptq" if is_gptq_dir(quantized_dir) else "autoawq"
+            read = read_gptq_config if self.format == "gptq" else read_quant_config
+            cfg, problems = read(quantized_dir)
             if problems:
                 raise ValueError("; ".join(f"{k}: {v}" for k, v in problems.items()))
             self._gs, self._sym = cfg["group_size"], cfg["symmetric"]
+            self._ckpt_format = cfg.get("checkpoint_format")
             self._where: Dict[str, object] = {}
             for shard in autoawq_files(quantized_dir):
                 h = safe_open(shard, framework="pt")
@@ -129,6 +139,10 @@ class QuantizedCheckpoint:
         layer = name[: -len(".weight")] if name.endswith(".weight") else None
         if layer is not None and all(f"{layer}.{k}" in self._where for k in _GEMM_KEYS):
             gemm = {k: self._where[f"{layer}.{k}"].get_tensor(f"{layer}.{k}") for k in _GEMM_KEYS}
+            if self.format == "gptq":
+                if f"{layer}.g_idx" in self._where:
+                    gemm["g_idx"] = self._where[f"{layer}.g_idx"].get_tensor(f"{layer}.g_idx")
+                return self.dequant.gptq(gemm, self._gs, self._sym, self._ckpt_format)
             return self.dequant.autoawq(gemm, self._gs, self._sym)
         if name in self._where:
             return self._where[name].get_tensor(name)

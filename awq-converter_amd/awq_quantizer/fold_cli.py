@@ -22,8 +22,8 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
                       act_samples: Dict[str, torch.Tensor] = None) -> int:
     """--fold_scales: the decoder blocks one by one (quantization/block_plan.py) — a block's members
     and producers read together (the next block read ahead on the reader pool), then
-    AWQQuantizer.quantize_block, export_autoawq per result and D2H; linears in no group take the
-    regular path (RTN).  A block that fails is copied unquantized (modules_to_not_convert) with its
+    AWQQuantizer.quantize_block, export_autoawq (or export_gptq) per result and D2H; linears in no group
+    take the regular path (RTN).  A block that fails is copied unquantized (modules_to_not_convert) with its
     norms and biases left unfolded.  Writes model.safetensors (folded norm weights and biases in
     place of the source's), the configs, and awq_scales.safetensors: every block's "scales".
     act_samples (--search_loss output, --clip_loss output): "<block prefix>.<group>.samples" -> token
@@ -78,7 +78,11 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
                                          clip_loss="output")
                 else:
                     out = quantizer.quantize_block(tensors, cfg.act_stats, block, **clip_kw, **loss_kw)
-                exported = {n: _to_cpu(quantizer.export_autoawq(r)) for n, r in out["results"].items()}
+                if cfg.export_gptq:
+                    exported = {n: _to_cpu(quantizer.export_gptq(r, cfg.export_gptq))
+                                for n, r in out["results"].items()}
+                else:
+                    exported = {n: _to_cpu(quantizer.export_autoawq(r)) for n, r in out["results"].items()}
                 host_folded = _to_cpu(out["folded"])
                 host_scales = _to_cpu(out["scales"])
             except Exception as e:  # noqa: BLE001  (the block's linears are copied unquantized)

@@ -37,6 +37,13 @@ def packed_shapes(shape, group_size: int, bits: int) -> dict:
     return row_shapes(*rows_k(shape), group_size, bits)
 
 
+def gptq_shapes(N: int, K: int, group_size: int) -> dict:
+    """Shapes of a 4-bit GPTQ-layout linear [N = out_features, K = in_features] (include/awq_hip.h
+    awq_export_gptq): packed along K in qweight, along N in qzeros."""
+    G = K // group_size
+    return {"qweight": (K // 8, N), "qzeros": (G, N // 8), "scales": (G, N), "g_idx": (K,), "G": G}
+
+
 def result_meta(bits: int, group_size: int, symmetric: bool, shape=None) -> dict:
     """The metadata tensors of a result dict: bits / group_size (int32 0-d), symmetric (bool 0-d)
     and, for packed results, the input's shape (int64)."""

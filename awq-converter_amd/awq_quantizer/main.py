@@ -50,7 +50,8 @@ from .stream import device_name, start_warmup
 from .model_loading import TensorInfo, load_model_from_hub
 from .quantization.linear_weights import CONV1D_MODEL_TYPES, is_linear_weight
 from .utils.logger import get_logger
-from .options import AUTOAWQ_NEEDS_4_BITS, act_clip_of, check_args, check_flags, parse_args, wants_samples
+from .options import (AUTOAWQ_NEEDS_4_BITS, CHECKPOINT_FORMATS, GPTQ_NEEDS_4_BITS, act_clip_of, check_args,
+                      check_flags, parse_args, wants_samples)
 from .output import ChunkWriter, _NullSink, finish_run, model_type_of, save_autoawq, writer_threads
 from .pipeline import STREAM_OPTS, TIMINGS, StreamSettings, _device_worker, new_quantizer
 # names that callers outside the package import from here
@@ -220,7 +221,8 @@ def _split_linear(args, index: List[TensorInfo], ordered: List[TensorInfo], mtyp
     linear = {i.name for i in ordered if is_linear_weight(i, args.group_size, mtype)}
     passthrough = [i for i in index if i.name not in linear]
     ordered = [i for i in ordered if i.name in linear]
-    logger.info(f"AutoAWQ export: {len(ordered)} linear weights quantized, {len(passthrough)} copied")
+    logger.info(f"{'GPTQ' if args.output_format == 'gptq' else 'AutoAWQ'} export: {len(ordered)} linear weights "
+                f"quantized, {len(passthrough)} copied")
     return ordered, passthrough
 
 
@@ -310,11 +312,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         logger.info("Preparing tensors for quantization")
         start = time.time()
         ordered = select_tensors(index, logger)
-        autoawq = args.output_format == "autoawq"
+        autoawq = args.output_format in CHECKPOINT_FORMATS     # a checkpoint export, in either layout
         mtype = model_type_of(loader) if autoawq else None
         err = check_args(args, world, len(devices), mtype)
         passthrough: List[TensorInfo] = []
-        if autoawq and err != AUTOAWQ_NEEDS_4_BITS:   # that refusal comes before the export is planned and logged
+        if autoawq and err not in (AUTOAWQ_NEEDS_4_BITS, GPTQ_NEEDS_4_BITS):   # that refusal comes before the export is planned and logged
             ordered, passthrough = _split_linear(args, index, ordered, mtype, logger)
         if err:
             logger.error(err)
@@ -338,8 +340,9 @@ def main(argv: Optional[List[str]] = None) -> int:
         elif args.scale_method == "awq":
             logger.warning("--scale_method awq without --act_stats: every weight is quantized RTN")
 
-        cfg = StreamSettings.from_args(args, packed=args.output_format in ("packed", "autoawq"),
-                                       export_autoawq=autoawq, act_stats=act_stats, act_clip=act_clip_of(args))
+        cfg = StreamSettings.from_args(args, packed=args.output_format in ("packed",) + CHECKPOINT_FORMATS,
+                                       export_autoawq=autoawq,
+                                       export_gptq=args.gptq_format if args.output_format == "gptq" else None, act_stats=act_stats, act_clip=act_clip_of(args))
         if args.fold_scales:
             from .fold_cli import _main_fold_scales
             return _main_fold_scales(args, cfg, loader, index, ordered, passthrough, devices[0], logger, start,

@@ -78,11 +78,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--save_safetensors", action="store_true", help="Save in safetensors format instead of pytorch format")
     p.add_argument("--chunk_size", type=int, default=10, help="Number of tensors to save in each chunk (for large models)")
     # extension (not in the reference)
-    p.add_argument("--output_format", type=str, default="reference", choices=["reference", "packed", "autoawq"],
+    p.add_argument("--output_format", type=str, default="reference", choices=["reference", "packed", "autoawq", "gptq"],
                    help="reference: int32 tensor_q/zero_points + fp16 scales per tensor (reference layout); "
                         "packed: int32 qweight/qzeros (bits-packed) + fp16 scales; "
                         "autoawq: a 4-bit checkpoint in AutoAWQ's GEMM layout (linear weights quantized, "
-                        "everything else copied) + quant_config.json")
+                        "everything else copied) + quant_config.json; "
+                        "gptq: the same in AutoGPTQ's 4-bit layout (desc_act false; --symmetric is honoured) + "
+                        "quantize_config.json")
+    p.add_argument("--gptq_format", type=str, default="gptq", choices=["gptq", "gptq_v2"],
+                   help="--output_format gptq: the checkpoint_format. gptq (v1, what transformers and vLLM read) "
+                        "stores zero point - 1 modulo 16; gptq_v2 stores the zero point itself")
     p.add_argument("--dist_output", type=str, default="per_rank", choices=["per_rank", "gather"],
                    help="torchrun mode: per_rank = every rank writes its own chunk files (rank 0 adds "
                         "metadata.json over all of them); gather = results sent to rank 0, which writes everything")
@@ -114,6 +119,10 @@ def act_clip_of(args) -> Optional[Dict[str, float]]:
 
 
 AUTOAWQ_NEEDS_4_BITS = "--output_format autoawq writes 4-bit checkpoints (AutoAWQ GEMM layout)"
+GPTQ_NEEDS_4_BITS = "--output_format gptq writes 4-bit checkpoints (AutoGPTQ layout, desc_act false)"
+GPTQ_ONE_PROCESS = "--output_format gptq runs in one process (it is not written under torchrun)"
+# the formats that write a loadable checkpoint: linear weights quantized, everything else copied
+CHECKPOINT_FORMATS = ("autoawq", "gptq")
 
 
 def check_flags(args) -> Optional[str]:
@@ -122,7 +131,7 @@ def check_flags(args) -> Optional[str]:
     if args.calib_ids and args.act_stats:
         return "--calib_ids and --act_stats are mutually exclusive: the statistics come from one of them"
     if args.fold_scales and (args.scale_method != "awq" or not has_stats(args)
-                             or args.output_format != "autoawq"):
+                             or args.output_format not in CHECKPOINT_FORMATS):
         return "--fold_scales needs --scale_method awq, --act_stats and --output_format autoawq"
     if args.search_loss == "output":
         if not args.fold_scales:
@@ -161,8 +170,13 @@ def check_args(args, world: int, n_devices: int, model_type: Optional[str]) -> O
         return err
     stats = has_stats(args)
     autoawq = args.output_format == "autoawq"
+    gptq = args.output_format == "gptq"
     if autoawq and args.bits != 4:
         return AUTOAWQ_NEEDS_4_BITS
+    if gptq and args.bits != 4:
+        return GPTQ_NEEDS_4_BITS
+    if gptq and world > 1:
+        return GPTQ_ONE_PROCESS
     if args.fold_scales:
         from .quantization.block_plan import SUPPORTED
         if model_type not in SUPPORTED:
@@ -183,6 +197,10 @@ def check_args(args, world: int, n_devices: int, model_type: Optional[str]) -> O
     if stats:
         if args.scale_method != "awq":
             return f"{'--calib_ids' if args.calib_ids else '--act_stats'} needs --scale_method awq"
+        if gptq and not args.fold_scales:
+            return ("--act_stats with --output_format gptq: the searched input scales must be folded "
+                    "into the ops producing each input first; use --output_format packed or reference "
+                    "(results carry 'input_scale'), or add --fold_scales")
         if autoawq and not args.fold_scales:
             return ("--act_stats with --output_format autoawq: the searched input scales must be folded "
                     "into the ops producing each input first; use --output_format packed or reference "

@@ -310,7 +310,7 @@ def autoawq_tensors(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passt
     tensors = {}
     for name, r in quantized.items():
         prefix = name[: -len(".weight")]
-        for f in ("qweight", "qzeros", "scales"):
+        for f in ("qweight", "qzeros", "scales") + (("g_idx",) if "g_idx" in r else ()):   # g_idx: the GPTQ layout
             tensors[f"{prefix}.{f}"] = r[f].contiguous()
     for info in list(passthrough) + list(failed):
         if overrides and info.name in overrides:
@@ -344,19 +344,57 @@ def write_autoawq_configs(output_dir: str, args, loader, not_converted: List[str
                        f"(modules_to_not_convert): {not_converted}")
 
 
+def write_gptq_configs(output_dir: str, args, loader, not_converted: List[str], zeros_at_0: Dict[str, int],
+                       logger=None) -> None:
+    """quantize_config.json (AutoGPTQ) and, when the source has one, config.json with a transformers
+    `quantization_config`.  zeros_at_0: layer -> zero points equal to 0, which checkpoint_format
+    "gptq" stores as 15 (loaders differ on masking after they add 1): warned about per tensor and
+    recorded under "zero_points_at_0"."""
+    qcfg = {"quant_method": "gptq", "bits": 4, "group_size": args.group_size, "sym": bool(args.symmetric),
+            "desc_act": False, "checkpoint_format": args.gptq_format}
+    if not_converted:
+        qcfg["modules_to_not_convert"] = list(not_converted)
+    zeros_at_0 = {k: int(v) for k, v in zeros_at_0.items() if int(v)}
+    meta = {"zero_points_at_0": sum(zeros_at_0.values()), "zero_points_at_0_per_tensor": zeros_at_0}
+    with open(os.path.join(output_dir, "quantize_config.json"), "w") as f:
+        json.dump(dict(qcfg, meta=meta), f, indent=2)
+    src = os.path.join(getattr(loader, "model_path", "") or "", "config.json")
+    if os.path.isfile(src):
+        with open(src) as f:
+            cfg = json.load(f)
+        cfg["quantization_config"] = dict(qcfg)
+        with open(os.path.join(output_dir, "config.json"), "w") as f:
+            json.dump(cfg, f, indent=2)
+    if logger:
+        for layer, n in zeros_at_0.items():
+            logger.warning(f"{layer}: {n} zero point(s) equal to 0 are stored as 15 (checkpoint_format gptq "
+                           f"stores zero - 1); a loader must mask to 4 bits after adding 1")
+        if not_converted:
+            logger.warning(f"{len(not_converted)} linear weight(s) failed to quantize and were copied unquantized "
+                           f"(modules_to_not_convert): {not_converted}")
+
+
 def save_autoawq(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthrough: List[TensorInfo],
                  output_dir: str, args, logger=None, failed: List[TensorInfo] = (),
                  overrides: Optional[Dict[str, torch.Tensor]] = None) -> None:
     """model.safetensors with `<layer>.qweight/.qzeros/.scales` for every quantized linear
     weight and every other tensor copied unchanged (linear weights that failed to quantize
     included, listed in modules_to_not_convert so the checkpoint still loads), plus the
-    configs of write_autoawq_configs."""
+    configs of write_autoawq_configs.  --output_format gptq: the results are export_gptq()'s
+    (`.g_idx` too) and the configs write_gptq_configs'."""
     from safetensors.torch import save_file
+    gptq = getattr(args, "output_format", None) == "gptq"
     tensors = autoawq_tensors(quantized, loader, passthrough, failed, overrides)
     save_file(tensors, os.path.join(output_dir, "model.safetensors"), metadata={"format": "pt"})
-    write_autoawq_configs(output_dir, args, loader, [i.name[: -len(".weight")] for i in failed], logger)
+    not_converted = [i.name[: -len(".weight")] for i in failed]
+    if gptq:
+        write_gptq_configs(output_dir, args, loader, not_converted,
+                           {n[: -len(".weight")]: int(r.get("zero_points_at_0", 0)) for n, r in quantized.items()},
+                           logger)
+    else:
+        write_autoawq_configs(output_dir, args, loader, not_converted, logger)
     if logger:
-        logger.info(f"Saved AutoAWQ checkpoint: {len(quantized)} quantized linear weights, "
+        logger.info(f"Saved {'GPTQ' if gptq else 'AutoAWQ'} checkpoint: {len(quantized)} quantized linear weights, "
                     f"{len(passthrough) + len(failed)} tensors copied")
 
 

@@ -41,7 +41,8 @@ class StreamSettings:
     memory_efficient: bool = False
     keep_on_device: bool = False
     batch_bytes: int = 1 << 30
-    export_autoawq: bool = False
+    export_autoawq: bool = False         # a checkpoint export: AutoAWQ's GEMM layout, or with export_gptq GPTQ's
+    export_gptq: Optional[str] = None    # the GPTQ checkpoint_format ("gptq" / "gptq_v2")
     act_stats: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None
     act_clip: Optional[Dict[str, float]] = None
     engine: str = "native"
@@ -229,7 +230,9 @@ def _quantize(cfg: StreamSettings, quantizer: AWQQuantizer, dev_in: Dict[str, to
         res = quantizer.quantize_model_device({n: t for n, t in dev_in.items()
                                                if not (act_stats and n in act_stats)}, packed=cfg.packed)
         res.update(searched)
-        if cfg.export_autoawq:
+        if cfg.export_gptq:
+            res = {n: _with_input_scale(quantizer.export_gptq(r, cfg.export_gptq), r) for n, r in res.items()}
+        elif cfg.export_autoawq:
             res = {n: _with_input_scale(quantizer.export_autoawq(r), r) for n, r in res.items()}
         ev_k = torch.cuda.Event()
         ev_k.record(compute)

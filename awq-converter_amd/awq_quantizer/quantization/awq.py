@@ -25,8 +25,8 @@ quantize_layer_group / quantize_block(loss="output") score the search by that er
 This module is the class: its state, its checks, the reference API and quantize_packed.  Every
 other method is a delegate to a function that takes the quantizer first — reference_private.py
 (the reference's private methods), batch.py (whole models), act_search.py (activation-aware),
-autoawq.py (AutoAWQ in and out), report.py (the error report) — imported when first called;
-shapes and result metadata come from ../layout.py.
+autoawq.py (AutoAWQ in and out), gptq.py (GPTQ in and out), report.py (the error report) — imported
+when first called; shapes and result metadata come from ../layout.py.
 """
 
 from typing import Dict, Optional, Tuple
@@ -494,6 +494,38 @@ class AWQQuantizer:
         """import_autoawq, then dequantize_packed: the [out, in] weight a GEMM-layout linear holds."""
         from .autoawq import dequantize_autoawq
         return dequantize_autoawq(self, gemm, group_size, symmetric, dtype)
+
+    def export_gptq(self, packed, checkpoint_format: str = "gptq") -> Dict[str, torch.Tensor]:
+        """A 2-D [out_features, in_features] weight in AutoGPTQ's 4-bit layout, desc_act = false
+        (include/awq_hip.h awq_export_gptq): `packed` is a quantize_packed() result, or the weight
+        itself (it is then quantized first).  qweight int32 [in/8, out] (nibble i of word (r, n) =
+        element 8r + i of row n), qzeros int32 [in/group_size, out/8], scales fp16
+        [in/group_size, out], g_idx int32 [in] = k // group_size; sequential nibbles, no
+        interleave.  Symmetric results keep their fields (q + 8, zero 8).  checkpoint_format
+        "gptq" (v1) stores zero - 1 modulo 16, "gptq_v2" the zero itself; "zero_points_at_0"
+        (int64 0-d, on the device) counts the zero points v1 stores as 15.  Device tensors."""
+        from .gptq import export_gptq
+        if isinstance(packed, torch.Tensor):
+            packed = self.quantize_packed(packed)
+        return export_gptq(self, packed, checkpoint_format)
+
+    def import_gptq(self, gptq: Dict[str, torch.Tensor], group_size: Optional[int] = None,
+                    symmetric: Optional[bool] = None, checkpoint_format: str = "gptq") -> Dict[str, torch.Tensor]:
+        """The inverse of export_gptq (include/awq_hip.h awq_import_gptq): `gptq` holds qweight,
+        qzeros and scales of one linear in the GPTQ layout (and optionally g_idx, which must be
+        k // group_size: act-order is not supported), on the CPU or the device.  Returns a
+        quantize_packed()-shaped dict on the device, as import_autoawq does.  ValueError for
+        inconsistent shapes, an unknown checkpoint_format or an act-order g_idx; RuntimeError for
+        what the C call refuses."""
+        from .gptq import import_gptq
+        return import_gptq(self, gptq, group_size, symmetric, checkpoint_format)
+
+    def dequantize_gptq(self, gptq: Dict[str, torch.Tensor], group_size: Optional[int] = None,
+                        symmetric: Optional[bool] = None, checkpoint_format: str = "gptq",
+                        dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """import_gptq, then dequantize_packed: the [out, in] weight a GPTQ-layout linear holds."""
+        from .gptq import dequantize_gptq
+        return dequantize_gptq(self, gptq, group_size, symmetric, checkpoint_format, dtype)
 
     def dequantize_packed(self, packed: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """Inverse of quantize_packed with the reference's dequantize arithmetic (fp16 math)."""

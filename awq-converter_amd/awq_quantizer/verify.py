@@ -20,7 +20,11 @@ index.json and the shards it names, in the AutoAWQ GEMM layout) are read back as
 measured against the source's <layer>.weight in the domain it was quantized in, rebuilt from
 awq_scales.safetensors when --fold_scales wrote one: first fold_rows(W, <layer>.weight.row_scale),
 then input_scale = <layer>.weight.input_scale (quantize_block's order); entries gain "row_folded"
-and "layout": "autoawq".  With a sidecar the fold itself is audited (fold_audit): one input scale
+and "layout": "autoawq".  --output_format gptq directories (the same files, with
+quantize_config.json saying quant_method "gptq") take the same audit through
+AWQQuantizer.import_gptq ("layout": "gptq"); a g_idx that is not k // group_size (act-order is
+not supported), a symmetric checkpoint with a stored zero other than 8, and a missing or unknown
+checkpoint_format are findings.  With a sidecar the fold itself is audited (fold_audit): one input scale
 per layer group, the folded norm weights and producer biases bit for bit.  Every other tensor must
 equal the source's bytes (report key "copied").  Any finding is a "problems" entry and makes the
 return code 1.  Checkpoints written by AutoAWQ itself are out of scope (parity unpinned).
@@ -222,6 +226,10 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
             dev = q().compute_device()
             return _hip.fold_rows(w.to(dev).contiguous(), s.to(dev, torch.float32).contiguous())
 
+        if is_gptq_dir(args.quantized_dir):     # import_fn also takes the checkpoint_format
+            return verify_autoawq(args, loader, index, error_fn,
+                                  import_fn or (lambda g, gs, sym, fmt: q().import_gptq(g, gs, sym, fmt)),
+                                  fold_fn or device_fold, logger, samples, layout="gptq")
         return verify_autoawq(args, loader, index, error_fn,
                               import_fn or (lambda gemm, gs, sym: q().import_autoawq(gemm, gs, sym)),
                               fold_fn or device_fold, logger, samples)
@@ -315,6 +323,81 @@ def read_quant_config(quantized_dir: str) -> Tuple[dict, Dict[str, str]]:
     return out, problems
 
 
+# ---------------------------------------------------------------- GPTQ directories
+GPTQ_FORMATS = ("gptq", "gptq_v2")
+
+
+def _gptq_settings(quantized_dir: str) -> Optional[dict]:
+    """quantize_config.json, else config.json's quantization_config, when it says quant_method
+    "gptq"; None otherwise."""
+    for fname, key in (("quantize_config.json", None), ("config.json", "quantization_config")):
+        try:
+            with open(os.path.join(quantized_dir, fname)) as f:
+                cfg = json.load(f)
+        except (OSError, ValueError):
+            continue
+        cfg = cfg.get(key) if key else cfg
+        if isinstance(cfg, dict) and cfg.get("quant_method") == "gptq":
+            return cfg
+    return None
+
+
+def is_gptq_dir(quantized_dir: str) -> bool:
+    """An --output_format gptq directory: the files of an autoawq one, and settings that say
+    quant_method "gptq"."""
+    return is_autoawq_dir(quantized_dir) and _gptq_settings(quantized_dir) is not None
+
+
+def read_gptq_config(quantized_dir: str) -> Tuple[dict, Dict[str, str]]:
+    """({"group_size", "symmetric", "checkpoint_format", "not_converted"}, problems) of a GPTQ
+    directory's settings."""
+    cfg = _gptq_settings(quantized_dir)
+    if cfg is None:
+        return {}, {"quantize_config.json": "cannot be read, or its quant_method is not 'gptq'"}
+    problems: Dict[str, str] = {}
+    if cfg.get("bits") != 4:
+        problems["quantize_config.json"] = f"bits {cfg.get('bits')!r}: only 4-bit GPTQ checkpoints are read"
+    gs = cfg.get("group_size")
+    if not isinstance(gs, int) or isinstance(gs, bool) or gs <= 0:
+        problems["quantize_config.json"] = f"group_size {gs!r} is not a positive integer"
+    if cfg.get("desc_act"):
+        problems["quantize_config.json"] = "desc_act is true: act-order checkpoints are not supported"
+    fmt = cfg.get("checkpoint_format")
+    if fmt not in GPTQ_FORMATS:
+        problems["quantize_config.json"] = (f"checkpoint_format {fmt!r} is missing or unknown (known: "
+                                            f"{', '.join(GPTQ_FORMATS)}): the stored zero points cannot be read")
+    out = {"group_size": gs, "symmetric": bool(cfg.get("sym", False)), "checkpoint_format": fmt,
+           "not_converted": list(cfg.get("modules_to_not_convert") or [])}
+    return out, problems
+
+
+def gptq_findings(gptq: Dict[str, torch.Tensor], group_size: int, symmetric: bool, checkpoint_format: str) -> List[str]:
+    """What verify reports of one GPTQ linear before it is imported: a g_idx that is not
+    k // group_size, and, symmetric, a stored zero point other than 8."""
+    out = []
+    g = gptq.get("g_idx")
+    K = int(gptq["qweight"].shape[0]) * 8
+    if g is None:
+        out.append("no g_idx")
+    else:
+        g = g.to(torch.int64).reshape(-1)
+        if g.numel() != K:
+            out.append(f"g_idx has {g.numel()} entries for in_features {K}")
+        else:
+            bad = (g != torch.arange(K, dtype=torch.int64) // group_size).nonzero().reshape(-1)
+            if bad.numel():
+                k = int(bad[0])
+                out.append(f"g_idx[{k}] = {int(g[k])}, not {k // group_size} = k // group_size at {bad.numel()} "
+                           f"position(s): act-order (desc_act) checkpoints are not supported")
+    if symmetric:
+        stored = (8 - (1 if checkpoint_format == "gptq" else 0)) * 0x11111111
+        stored -= (1 << 32) if stored >= (1 << 31) else 0
+        bad = int((gptq["qzeros"].to(torch.int32) != stored).sum())
+        if bad:
+            out.append(f"symmetric checkpoint with a stored zero point other than 8 in {bad} qzeros word(s)")
+    return out
+
+
 def same_bytes(a: torch.Tensor, b: torch.Tensor) -> bool:
     """Equal dtype, shape and bytes (so NaN payloads and signed zeros count)."""
     if a.dtype != b.dtype or a.shape != b.shape:
@@ -402,15 +485,18 @@ def audited_tensors(shapes: Dict[str, Tuple[int, ...]], model_type: Optional[str
 
 def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], error_fn: Callable,
                    import_fn: Callable, fold_fn: Callable, logger,
-                   samples: Optional[Dict[str, torch.Tensor]] = None) -> int:
+                   samples: Optional[Dict[str, torch.Tensor]] = None, layout: str = "autoawq") -> int:
     """verify() for an --output_format autoawq directory (see the module docstring).
-    import_fn(gemm, group_size, symmetric) -> quantize_packed()-shaped dict; fold_fn(w, s) = fold_rows."""
+    import_fn(gemm, group_size, symmetric) -> quantize_packed()-shaped dict; fold_fn(w, s) = fold_rows.
+    layout "gptq": an --output_format gptq directory, the same audit; import_fn then also takes
+    the checkpoint_format, and gptq_findings() are problems of their linear."""
     from safetensors import safe_open
     d = args.quantized_dir
     entries: Dict[str, dict] = {}
     skipped: Dict[str, str] = {}
     copied: List[str] = []
-    cfg, problems = read_quant_config(d)
+    gptq = layout == "gptq"
+    cfg, problems = read_gptq_config(d) if gptq else read_quant_config(d)
 
     def problem(name: str, why: str) -> None:
         problems[name] = why
@@ -422,7 +508,7 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
         for name, why in problems.items():
             logger.error(f"{name}: {why}")
         loader.close()
-        write_report(path, entries, problems, echo, skipped, extra={"layout": "autoawq", "copied": copied,
+        write_report(path, entries, problems, echo, skipped, extra={"layout": layout, "copied": copied,
                                                                     "fold_audited": False})
         return 1
     handles = []
@@ -442,7 +528,7 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
         read_ckpt = lambda n: where[n].get_tensor(n) if n in where else None
         layers = sorted({n.rpartition(".")[0] for n in where if n.rpartition(".")[2] in _GEMM_KEYS
                          and all(f"{n.rpartition('.')[0]}.{k}" in where for k in _GEMM_KEYS)})
-        in_triple = {f"{l}.{k}" for l in layers for k in _GEMM_KEYS}
+        in_triple = {f"{l}.{k}" for l in layers for k in _GEMM_KEYS + (("g_idx",) if gptq else ())}
         for layer in layers:
             name = f"{layer}.weight"
             info = index.get(name)
@@ -453,13 +539,25 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
                 problem(name, "quantized although quant_config.json lists it in modules_to_not_convert")
                 continue
             gemm = {k: read_ckpt(f"{layer}.{k}") for k in _GEMM_KEYS}
-            shape = (int(gemm["qweight"].shape[1]) * 8, int(gemm["qweight"].shape[0])) \
-                if gemm["qweight"].dim() == 2 else tuple(gemm["qweight"].shape)
+            if gemm["qweight"].dim() != 2:
+                shape = tuple(gemm["qweight"].shape)
+            elif gptq:
+                shape = (int(gemm["qweight"].shape[1]), int(gemm["qweight"].shape[0]) * 8)
+            else:
+                shape = (int(gemm["qweight"].shape[1]) * 8, int(gemm["qweight"].shape[0]))
             if tuple(info.shape) != shape:
                 problem(name, f"shape {list(shape)} != source shape {list(info.shape)}")
                 continue
             try:
-                res = import_fn(gemm, cfg["group_size"], cfg["symmetric"])
+                if gptq:
+                    gemm["g_idx"] = read_ckpt(f"{layer}.g_idx")
+                    found = gptq_findings(gemm, cfg["group_size"], cfg["symmetric"], cfg["checkpoint_format"])
+                    if found:
+                        problem(name, "; ".join(found))
+                        continue
+                    res = import_fn(gemm, cfg["group_size"], cfg["symmetric"], cfg["checkpoint_format"])
+                else:
+                    res = import_fn(gemm, cfg["group_size"], cfg["symmetric"])
                 w = loader.read(info)
                 row_scale = sidecar.get(f"{name}.row_scale")
                 if row_scale is not None:
@@ -473,7 +571,7 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
                 continue
             entries[name] = {k: e[k] for k in _ENTRY_KEYS}
             entries[name].update(input_scaled=in_scale is not None, row_folded=row_scale is not None,
-                                 layout="autoawq")
+                                 layout=layout)
             entries[name].update(output_entry(e))
             logger.info(f"{name}: mean_abs_error {e['mean_abs_error']:.6g}  max {e['max_abs_error']:.6g}  "
                         f"snr {e['snr_db']:.2f} dB  nonfinite {e['nonfinite']}")
@@ -512,7 +610,7 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
         del handles
     log_worst(entries, args.worst, logger)
     report = write_report(path, entries, problems, echo, skipped,
-                          extra={"layout": "autoawq", "copied": copied, "fold_audited": has_sidecar})
+                          extra={"layout": layout, "copied": copied, "fold_audited": has_sidecar})
     t = report["totals"]
     logger.info(f"{t['tensors']} tensors, {t['numel']} elements: mean_abs_error {t['mean_abs_error']:.6g}  "
                 f"snr {t['snr_db']:.2f} dB  nonfinite {t['nonfinite']}; {len(copied)} copied; report: {path}")

@@ -274,6 +274,38 @@ int awq_import_autoawq_gemm(const int32_t* qweight_t, const int32_t* qzeros_t, c
                             int64_t K, int64_t group_size, int bits, int32_t* qweight, int32_t* qzeros,
                             uint16_t* scales, void* stream);
 
+/* ---- AutoGPTQ layout, 4 bits, desc_act = false (additive to ABI 17): from this
+ * library's row-major packed 4-bit results of an [N = out_features, K = in_features] weight
+ * (qweight [N, K/8], qzeros [N, ceil(G/8)], scales fp16 [N, G], G = K / group_size) to
+ *   qweight_t int32 [K/8, N]   nibble i of word (r, n) = u[n, 8r + i]   (sequential, no interleave)
+ *   qzeros_t  int32 [G, N/8]   nibble i of word (g, c) = zs[g, 8c + i]  (sequential)
+ *   scales_t  fp16  [G, N]     the scale bits, transposed
+ *   g_idx     int32 [K]        k / group_size
+ * A packed field of this library is q - qmin: u = q and z' = z when asymmetric, u = q + 8 and
+ * z' = 8 when symmetric ((u - z') s = q s exactly), so u and z' are the stored fields in both
+ * modes and `symmetric` (0 or 1) changes no bit of the transform.  zero_offset selects the stored
+ * zero: 1 (checkpoint_format "gptq", v1) zs = (z' - 1) & 15; 0 ("gptq_v2") zs = z'.
+ * Checked in this order, nothing launched on a failure: a negative N or K: AWQ_EINVAL; bits != 4:
+ * AWQ_EUNSUPPORTED; group_size <= 0, N % 8, K % 8 or K % group_size != 0: AWQ_EINVAL; zero_offset
+ * or symmetric outside {0, 1}: AWQ_EINVAL; N == 0 or K == 0: AWQ_OK, no pointer is looked at; N or
+ * K above 65535 * 256 (the AutoAWQ export's limit) or N K > 2^42: AWQ_EUNSUPPORTED; no output:
+ * AWQ_EINVAL; an output whose input is NULL: AWQ_EINVAL.  Any output may be NULL (its input is
+ * then not read); at least one must not be.  Caller-owned device memory on the caller's stream;
+ * no allocation, no sync.  Pointers need 4-B (scales: 2-B) alignment; 16-B aligned ones with
+ * K % 32 == 0 (scales: G % 8 == 0) take 16-B accesses, which give the same bits. */
+int awq_export_gptq(const int32_t* qweight, const int32_t* qzeros, const uint16_t* scales, int64_t N, int64_t K,
+                    int64_t group_size, int bits, int symmetric, int zero_offset, int32_t* qweight_t,
+                    int32_t* qzeros_t, uint16_t* scales_t, int32_t* g_idx, void* stream);
+
+/* The exact inverse of awq_export_gptq with the same zero_offset: import(export(p)) == p word for
+ * word; z' = (zs + zero_offset) & 15, and the unused high fields of a row's last qzeros word
+ * (G % 8 != 0) are 0.  The same checks in the same order.  Nothing on the device is refused: a
+ * symmetric checkpoint whose stored zero is not 8 imports as it is stored (the Python reader
+ * reports it); g_idx is not an input (act-order is not supported). */
+int awq_import_gptq(const int32_t* qweight_t, const int32_t* qzeros_t, const uint16_t* scales_t, int64_t N, int64_t K,
+                    int64_t group_size, int bits, int symmetric, int zero_offset, int32_t* qweight, int32_t* qzeros,
+                    uint16_t* scales, void* stream);
+
 /* Measurement helper: copy `bytes` (multiple of 16, 16-B aligned buffers) with the
  * quantizer's memory structure (one wave per 4 KiB, 16-B nt loads/stores); bench.py
  * quotes the kernel against this copy's rate. */
