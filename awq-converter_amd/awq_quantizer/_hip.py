@@ -108,6 +108,7 @@ SIGNATURES = {
     "awq_import_autoawq_gemm": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _P, _P, _P, _P]),
     "awq_export_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "awq_import_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "awq_gptq_round_block": (_I32, [_P, _I64, _I64, _I64, _I32, _I32, _P, _I64, _I64, _P, _P, _P, _P, _P]),
     "awq_plan_block_tensor": (_I64, [ctypes.POINTER(TensorDesc), _I32, _I64, _P, _I64]),
     "awq_ragged_flags": (_I32, [ctypes.POINTER(TensorDesc), _I32, _I64]),
     "awq_quantize_ragged": (_I32, [_P, _I32, _I64, _P, _I32, _I32, _I32, _I64, _I32, _P]),
@@ -456,6 +457,26 @@ def import_gptq(qweight_t, qzeros_t, scales_t, N: int, K: int, L: int, bits: int
                                         zero_offset, ptr(qweight), ptr(qzeros), ptr(scales),
                                         ctypes.c_void_p(stream_ptr(dev)))
     check(rc, "awq_import_gptq")
+
+
+GPTQ_BLOCK = 128         # columns per awq_gptq_round_block call at most (include/awq_hip.h)
+
+
+def gptq_round_block(work: torch.Tensor, u: torch.Tensor, L: int, bits: int, symmetric: bool, col_begin: int,
+                     n_cols: int, err: torch.Tensor, qweight, qzeros, scales) -> None:
+    """awq_gptq_round_block: GPTQ's in-block loop on columns [col_begin, col_begin + n_cols) of the
+    fp32 working weights work [N, K] (device, contiguous, updated in place) with the fp32 [K, K]
+    upper factor u of the inverse Hessian; err fp32 [N, n_cols] receives the scaled errors, and the
+    block's words, zero fields and scales of the packed result are written (qzeros zero-filled by
+    the caller before the first block)."""
+    N, K = work.shape
+    for t, dt, shape, what in ((work, torch.float32, (N, K), "work"), (u, torch.float32, (K, K), "u"),
+                               (err, torch.float32, (N, n_cols), "err")):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != work.device:
+            raise ValueError(f"awq_gptq_round_block: {what} must be a contiguous {dt} {shape} on {work.device}")
+    check(load_library().awq_gptq_round_block(ptr(work), N, K, L, bits, int(bool(symmetric)), ptr(u), col_begin, n_cols,
+                                              ptr(err), ptr(qweight), ptr(qzeros), ptr(scales), _stream(work)),
+          "awq_gptq_round_block")
 
 
 def dequantize(tensor_q, scales, zeros, rows, K, L, out) -> None:

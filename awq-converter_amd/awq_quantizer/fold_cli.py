@@ -26,9 +26,10 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
     take the regular path (RTN).  A block that fails is copied unquantized (modules_to_not_convert) with its
     norms and biases left unfolded.  Writes model.safetensors (folded norm weights and biases in
     place of the source's), the configs, and awq_scales.safetensors: every block's "scales".
-    act_samples (--search_loss output, --clip_loss output): "<block prefix>.<group>.samples" -> token
-    samples; each block's four tensors go to quantize_block, with loss="output" and / or
-    clip_loss="output"."""
+    act_samples (--search_loss output, --clip_loss output, --rounding gptq): "<block prefix>.<group>.samples"
+    -> token samples; each block's four tensors go to quantize_block, with loss="output" and / or
+    clip_loss="output"; --rounding gptq sets the quantizer's rounding / gptq_damp and logs every weight's
+    output error, round-to-nearest -> compensated."""
     from safetensors.torch import save_file
     from .quantization.act_search import quantize_block
     from .quantization.block_plan import plan_blocks
@@ -41,6 +42,9 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
     except Exception as e:  # noqa: BLE001
         logger.error(f"Quantization on {device} failed: {e}")
         return 1
+    gptq = getattr(args, "rounding", "nearest") == "gptq" and act_samples is not None
+    if gptq:    # settings of the quantizer, as clip_loss is: quantize_block's signature is pinned
+        quantizer.rounding, quantizer.gptq_damp = "gptq", args.gptq_damp
     clip_kw = {"clip": True, **cfg.act_clip} if cfg.act_clip else {}
     output_loss = act_samples is not None and args.search_loss == "output"
     output_clip = act_samples is not None and bool(cfg.act_clip) and args.clip_loss == "output"
@@ -69,7 +73,7 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
             try:
                 tensors = {n: f.result() for n, f in futs.pop(k).items()}
                 loss_kw = {}
-                if output_loss or output_clip:
+                if output_loss or output_clip or gptq:
                     smp = {g: act_samples[f"{block.prefix}.{g}.samples"] for g in block.groups
                            if f"{block.prefix}.{g}.samples" in act_samples}
                     loss_kw = {"samples": smp, **({"loss": "output"} if output_loss else {})}
@@ -97,6 +101,10 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
                 if g.get("clip"):
                     logger.info(f"{block.prefix}.{gname}: clip loss {g['clip'].get('loss', 'diag')}, "
                                 f"{g['clip']['loss_before']:.6g} -> {g['clip']['loss_after']:.6g}")
+                for m, rd in (g.get("rounding") or {}).items():
+                    if rd["loss"] is not None:
+                        logger.info(f"{m}: gptq rounding, output error {rd['loss_rtn']:.6g} -> {rd['loss']:.6g}"
+                                    f"{' (fallback: nearest)' if rd['fallback'] else ''}")
                 if g.get("loss"):
                     logger.info(f"{block.prefix}.{gname}: search loss {g['loss']}, winner {g['best']}/"
                                 f"{args.search_grid} (diagonal loss: {g['diag_best']}/{args.search_grid})")

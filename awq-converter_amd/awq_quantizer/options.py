@@ -59,6 +59,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--clip_grid", type=int, default=20, help="--act_clip: grid size of the range shrinks")
     p.add_argument("--clip_max_shrink", type=float, default=0.5,
                    help="--act_clip: largest shrink of the group range tried")
+    p.add_argument("--rounding", type=str, default="nearest", choices=["nearest", "gptq"],
+                   help="--fold_scales: how the fields are chosen once the scales are. nearest: round to nearest; "
+                        "gptq: GPTQ's error-compensated rounding on token samples (--act_samples, or collected by the "
+                        "--calib_ids forward) after the scale search; not with --act_clip")
+    p.add_argument("--gptq_damp", type=float, default=0.01,
+                   help="--rounding gptq: the fraction of the Hessian's mean diagonal added to its diagonal")
     p.add_argument("--per_channel", action="store_true", help="Use per-channel quantization")
     p.add_argument("--device", type=str, default="cuda" if torch.cuda.is_available() else "cpu",
                    help="Device to use for quantization (cuda, cuda:0, cuda:1, cpu, or 'all' for all GPUs)")
@@ -104,8 +110,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
 
 
 def wants_samples(args) -> bool:
-    """A search of this run scores its candidates on token samples."""
-    return args.search_loss == "output" or args.clip_loss == "output"
+    """A search of this run scores its candidates on token samples, or --rounding gptq solves on them."""
+    return args.search_loss == "output" or args.clip_loss == "output" or getattr(args, "rounding", "nearest") == "gptq"
 
 
 def has_stats(args) -> bool:
@@ -157,6 +163,20 @@ def check_flags(args) -> Optional[str]:
             return "--n_sample_tokens must be positive"
     if args.act_samples and not wants_samples(args):
         return "--act_samples is read by --search_loss output"
+    if getattr(args, "rounding", "nearest") == "gptq":
+        if not args.fold_scales:
+            return "--rounding gptq needs --fold_scales (and so --scale_method awq and a checkpoint --output_format)"
+        if args.act_samples and args.calib_ids:
+            return "--act_samples and --calib_ids both give token samples: the samples come from one of them"
+        if not args.act_samples and not args.calib_ids:
+            return ("--rounding gptq needs token samples: --act_samples FILE (awq_quantizer.calibrate "
+                    "--samples_output), or --calib_ids")
+        if args.calib_ids and args.n_sample_tokens <= 0:
+            return "--n_sample_tokens must be positive"
+        if args.act_clip:
+            return "--rounding gptq refuses --act_clip: the solver moves the ranges the clip search chose"
+        if not 0.0 < getattr(args, "gptq_damp", 0.01) < 1.0:
+            return "--gptq_damp must be in (0, 1)"
     return None
 
 

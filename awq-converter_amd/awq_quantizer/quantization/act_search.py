@@ -104,6 +104,24 @@ def _check_args(q, what: str, loss: str, clip_loss: Optional[str] = None) -> str
     return clip_loss
 
 
+def _check_rounding(q, what: str, clip: bool) -> bool:
+    """The quantizer's rounding attribute ("nearest" / "gptq"; AWQQuantizer's methods have no such
+    argument).  -> whether the groups with token samples take quantize_gptq."""
+    rounding = getattr(q, "rounding", "nearest")
+    if rounding not in ("nearest", "gptq"):
+        raise ValueError(f"rounding must be 'nearest' or 'gptq': {rounding!r}")
+    if rounding == "gptq" and clip:
+        raise ValueError(f"{what}: clip=True with rounding='gptq': the solver moves the ranges the clip search chose")
+    return rounding == "gptq"
+
+
+def _log_rounding(q, name: str, r: dict) -> None:
+    rd = r["rounding"]
+    if rd["loss"] is not None:
+        q.logger.info(f"gptq rounding {name}: output error {rd['loss_rtn']:.6g} -> {rd['loss']:.6g}, damp {rd['damp']:g}"
+                      f"{', fallback to nearest' if rd['fallback'] else ''}")
+
+
 def _quantize_scaled(q, w: torch.Tensor, s: torch.Tensor, one_pass: bool, out: Optional[dict] = None,
                      scaled: Optional[torch.Tensor] = None) -> dict:
     """W * diag(s) as a quantize_packed() result.  `one_pass` (the shape is scaled_eligible) and a
@@ -130,6 +148,14 @@ def quantize_layer_group(q, weights: Dict[str, torch.Tensor], activations: Optio
     `activations`); None: the quantizer's clip_loss attribute.  The "clip" dict of an "output" run
     has the same keys plus "loss": "output", its losses are output-space losses."""
     clip_loss = _check_args(q, "quantize_layer_group", loss, clip_loss)
+    gptq = _check_rounding(q, "quantize_layer_group", clip)
+    gptq_samples = None
+    if gptq:
+        if not packed:
+            raise ValueError("rounding='gptq' writes packed outputs only (packed=False is not available)")
+        gptq_samples = activations if samples is None else samples
+        if gptq_samples is None:
+            q.logger.warning(f"rounding='gptq' without token samples for {list(weights)}: rounding to nearest")
     if loss == "output":
         samples = activations if samples is None else samples
         if samples is None:
@@ -156,7 +182,8 @@ def quantize_layer_group(q, weights: Dict[str, torch.Tensor], activations: Optio
         _hip.scaled_eligible(w.dtype, w.shape[0], w.shape[1], q.group_size) for w in weights.values()))
     sr = search_layer_group(weights, dev, group_size=q.group_size, bits=q.bits, symmetric=q.symmetric,
                             n_grid=q.search_grid, duo_scaling=q.duo_scaling, activations=activations,
-                            x_mean=x_mean, x_sq=x_sq, table=table, scale_weights=not one_pass)
+                            x_mean=x_mean, x_sq=x_sq, table=table,
+                            scale_weights=not one_pass and gptq_samples is None)
     extra = {}
     if loss == "output":
         sr = output_search(q, sr, samples)
@@ -166,7 +193,10 @@ def quantize_layer_group(q, weights: Dict[str, torch.Tensor], activations: Optio
     results, s, scaled = {}, sr["input_scale"], sr["scaled"] or {}
     for name in weights:
         w = sr["weights"][name]
-        if packed:
+        if gptq_samples is not None:              # the solver scales the weight and the samples itself
+            r = q.quantize_gptq(w, gptq_samples, input_scale=s, damp=getattr(q, "gptq_damp", 0.01))
+            _log_rounding(q, name, r)
+        elif packed:
             r = _quantize_scaled(q, w, s, one_pass, scaled=scaled.get(name))
         else:                                     # RTN of W * diag(s), the reference's result dict
             r = q._quantize_device(scaled[name] if name in scaled else _hip.apply_input_scale(w, s))
@@ -277,6 +307,7 @@ def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[t
     clip_loss="output" (with clip=True): every group with token samples takes the output-space clip
     loss, folded or not; a group without samples the diagonal one, with a warning."""
     clip_loss = _check_args(q, "quantize_block", loss, clip_loss)
+    gptq = _check_rounding(q, "quantize_block", clip)
     q._check_mode()
     dev = q.compute_device()
     clip_kw = {"clip": True, "clip_grid": clip_grid, "clip_max_shrink": clip_max_shrink} if clip else {}
@@ -323,23 +354,36 @@ def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[t
                 else:
                     how = "output"
                     loss_kw["samples"] = smp
+            if gptq and (samples or {}).get(g.name) is not None:
+                loss_kw["samples"] = samples[g.name]
             if how == getattr(q, "clip_loss", "diag"):    # the method resolves to the same choice: the call as it
                 out = q.quantize_layer_group(weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw, **loss_kw)
             else:                                         # was (an override of the method is honoured)
                 out = quantize_layer_group(q, weights, x_mean=st[0], x_sq=st[1], table=table, **clip_kw, **loss_kw,
                                            clip_loss=how)
             for m, r in out["results"].items():
-                results[m] = {k: v for k, v in r.items() if k != "input_scale"}
+                results[m] = {k: v for k, v in r.items() if k not in ("input_scale", "rounding")}
             s = out["input_scale"]
             report[g.name] = {"ratio": out["ratio"] if fold else None, "losses": out["losses"] if fold else None,
                               "folded": fold, "clip": out.get("clip")}
+            if gptq:
+                report[g.name]["rounding"] = {m: r["rounding"] for m, r in out["results"].items() if "rounding" in r}
             if loss_kw.get("loss"):
                 report[g.name].update(loss="output", best=out["best"], diag_best=out["diag_best"])
         else:
-            for m, w in weights.items():
-                results[m] = q.quantize_packed(w)
-            s = torch.ones(K, dtype=torch.float32, device=dev)
+            smp = (samples or {}).get(g.name) if gptq else None
+            if gptq and smp is None:
+                q.logger.warning(f"{g.name}: no token samples for rounding='gptq': rounding to nearest")
             report[g.name] = {"ratio": None, "losses": None, "folded": False, "clip": None}
+            for m, w in weights.items():
+                if smp is None:
+                    results[m] = q.quantize_packed(w)
+                    continue
+                r = q.quantize_gptq(w, smp, damp=getattr(q, "gptq_damp", 0.01))
+                _log_rounding(q, m, r)
+                report[g.name].setdefault("rounding", {})[m] = r.pop("rounding")
+                results[m] = r
+            s = torch.ones(K, dtype=torch.float32, device=dev)
         for m in g.members:
             scales[f"{m}.input_scale"] = s
         return s if fold else None

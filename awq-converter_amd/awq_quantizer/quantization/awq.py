@@ -25,8 +25,9 @@ quantize_layer_group / quantize_block(loss="output") score the search by that er
 This module is the class: its state, its checks, the reference API and quantize_packed.  Every
 other method is a delegate to a function that takes the quantizer first — reference_private.py
 (the reference's private methods), batch.py (whole models), act_search.py (activation-aware),
-autoawq.py (AutoAWQ in and out), gptq.py (GPTQ in and out), report.py (the error report) — imported
-when first called; shapes and result metadata come from ../layout.py.
+autoawq.py (AutoAWQ in and out), gptq.py (GPTQ in and out), gptq_round.py (GPTQ's error-compensated
+rounding), report.py (the error report) — imported when first called; shapes and result metadata
+come from ../layout.py.
 """
 
 from typing import Dict, Optional, Tuple
@@ -50,6 +51,14 @@ class AWQQuantizer:
     # activations=).  A setting of the quantizer, like search_grid: set it on the instance.
     # act_search.quantize_layer_group / quantize_block also take it per call (clip_loss=).
     clip_loss = "diag"
+
+    # quantize_layer_group / quantize_block: how the fields are chosen once the scales are.
+    # "nearest": round to nearest; "gptq": every member of a group that has token samples goes
+    # through quantize_gptq(w, samples, input_scale=s, damp=gptq_damp) after the scale search (a
+    # group without samples rounds to nearest, with a warning; clip=True is refused: the solver
+    # moves the ranges the clip chose).  Settings of the quantizer, like clip_loss.
+    rounding = "nearest"
+    gptq_damp = 0.01
 
     def __init__(
         self,
@@ -526,6 +535,32 @@ class AWQQuantizer:
         """import_gptq, then dequantize_packed: the [out, in] weight a GPTQ-layout linear holds."""
         from .gptq import dequantize_gptq
         return dequantize_gptq(self, gptq, group_size, symmetric, checkpoint_format, dtype)
+
+    def quantize_gptq(self, tensor: torch.Tensor, samples: Optional[torch.Tensor] = None, *,
+                      hessian: Optional[torch.Tensor] = None, input_scale: Optional[torch.Tensor] = None,
+                      damp: float = 0.01) -> Dict[str, torch.Tensor]:
+        """quantize_packed with GPTQ's error-compensated rounding instead of round-to-nearest
+        (gptq_round.py; include/awq_hip.h awq_gptq_round_block): a 2-D
+        [out_features, in_features] bf16 / fp16 / fp32 weight, group_size 32 / 64 / 128 dividing
+        in_features, static groups (no act-order).
+
+        samples [tokens, in_features]: token samples of the linear's input; H = X^T X is formed
+        from them in fp32 on the device.  hessian [in, in] replaces it (samples are then only
+        used for the report).  A column with H[c][c] == 0 gets H[c][c] = 1 and its working weight
+        zeroed; damp * mean(diag H) is added to the diagonal; U = cholesky(cholesky_inverse(
+        cholesky(H)), upper) (torch.linalg on the device).  Blocks of 128 columns: the kernel,
+        then one GEMM takes the block's errors off the columns to its right.
+        input_scale s fp32 [in] (quantize_layer_group's): the weight is W * diag(s)
+        (awq_apply_input_scale) and the samples X * diag(RN(1 / s)).
+
+        Returns the quantize_packed() dict (device tensors; "input_scale" when one was given) plus
+        "rounding": {"loss", "loss_rtn": the output error sum ((W^ - W) X^T)^2 of the result and of
+        round-to-nearest on the samples (awq_output_error, in the original domain; None without
+        samples), "dead_columns", "damp" (the value used), "fallback"}.  A failed factorisation
+        multiplies damp by 10, three tries in all; after that, and for a non-finite weight or
+        Hessian, the result is quantize_packed's, with a warning and fallback = True."""
+        from .gptq_round import quantize_gptq
+        return quantize_gptq(self, tensor, samples, hessian=hessian, input_scale=input_scale, damp=damp)
 
     def dequantize_packed(self, packed: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """Inverse of quantize_packed with the reference's dequantize arithmetic (fp16 math)."""

@@ -306,6 +306,38 @@ int awq_import_gptq(const int32_t* qweight_t, const int32_t* qzeros_t, const uin
                     int64_t group_size, int bits, int symmetric, int zero_offset, int32_t* qweight, int32_t* qzeros,
                     uint16_t* scales, void* stream);
 
+/* ---- GPTQ error-compensated rounding, one block of input columns (additive to ABI 17; no reference
+ * counterpart) ----
+ * Rounds columns [col_begin, col_begin + n_cols) of the fp32 working weights work [N, K] one column
+ * at a time and takes each column's error off the block's later columns through u, the fp32 [K, K]
+ * row-major upper-triangular factor with H^-1 = u^T u (H: the damped Hessian X^T X of the layer's
+ * input).  The caller then updates the columns right of the block (work[:, c1:] -= err u[c0:c1, c1:])
+ * and calls the next block; qweight / qzeros / scales are this library's packed result of the WHOLE
+ * [N, K] tensor (the layouts at the top of this file), of which a call writes only its block's
+ * qweight words, zero FIELDS (a read-modify-write of the word: the caller zero-fills qzeros once, so
+ * the pad fields of a row's last word are 0) and fp16 scales.
+ * Per row, for i = 0 .. n_cols - 1, c = col_begin + i, every operation a single fp32 operation:
+ *   at a group's first column: (scale, zero) = this library's fp32 rule (awq_quantize_groups on fp32
+ *     input) on the group's group_size working values as they stand now; the scale's fp16 bits are
+ *     stored as that entry stores them, and s = (float)fp16(scale) is what the steps below use;
+ *   quo = w[i] / s (IEEE), q = clamp(rint(quo) + zero, qmin, qmax), dq = (q - zero) s; a NaN
+ *     rint(quo) + zero stores the NaN field (INT32_MIN - qmin) & mask and dq = NaN;
+ *   e = (w[i] - dq) / u[c][c] (IEEE), e = 0 when s, dq or quo is not finite (a constant, NaN or inf
+ *     group propagates nothing); err[row, i] = e;
+ *   for j > i in the block: w[j] = RN(w[j] - RN(e u[c][col_begin + j])), no contraction.
+ * work's block columns hold the final w (a rounded column keeps the value it was rounded from).
+ * bits 4 / 8, symmetric 0 / 1, group_size 32 / 64 / 128.  Checked in this order, nothing launched on
+ * a failure: a negative N, K, col_begin or n_cols (AWQ_EINVAL); bits (AWQ_EUNSUPPORTED); symmetric
+ * outside {0, 1} (AWQ_EINVAL); group_size (AWQ_EUNSUPPORTED); K % group_size; n_cols > 128 or
+ * n_cols % group_size; col_begin % group_size, col_begin % 8 or col_begin + n_cols > K (AWQ_EINVAL);
+ * N, K or n_cols of 0: AWQ_OK, no pointer is looked at; N or K >= 2^31 (AWQ_EUNSUPPORTED); a NULL
+ * pointer; work, u or err not 16-B aligned, qweight / qzeros not 4-B, scales not 2-B (AWQ_EINVAL).
+ * err fp32 [N, n_cols].  One lane per row, one workgroup per 64 rows, the grid is not capped.
+ * Caller-owned device memory on the caller's stream; no allocation, no sync. */
+int awq_gptq_round_block(float* work, int64_t N, int64_t K, int64_t group_size, int bits, int symmetric,
+                         const float* u, int64_t col_begin, int64_t n_cols, float* err, int32_t* qweight,
+                         int32_t* qzeros, uint16_t* scales, void* stream);
+
 /* Measurement helper: copy `bytes` (multiple of 16, 16-B aligned buffers) with the
  * quantizer's memory structure (one wave per 4 KiB, 16-B nt loads/stores); bench.py
  * quotes the kernel against this copy's rate. */
