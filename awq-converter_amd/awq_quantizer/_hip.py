@@ -109,6 +109,8 @@ SIGNATURES = {
     "awq_export_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "awq_import_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
     "awq_gptq_round_block": (_I32, [_P, _I64, _I64, _I64, _I32, _I32, _P, _I64, _I64, _P, _P, _P, _P, _P]),
+    "awq_gptq_factor": (_I32, [_P, _I64, ctypes.c_float, _P, _I64, _P, _P]),
+    "awq_gptq_factor_workspace": (_I64, [_I64]),
     "awq_plan_block_tensor": (_I64, [ctypes.POINTER(TensorDesc), _I32, _I64, _P, _I64]),
     "awq_ragged_flags": (_I32, [ctypes.POINTER(TensorDesc), _I32, _I64]),
     "awq_quantize_ragged": (_I32, [_P, _I32, _I64, _P, _I32, _I32, _I32, _I64, _I32, _P]),
@@ -477,6 +479,21 @@ def gptq_round_block(work: torch.Tensor, u: torch.Tensor, L: int, bits: int, sym
     check(load_library().awq_gptq_round_block(ptr(work), N, K, L, bits, int(bool(symmetric)), ptr(u), col_begin, n_cols,
                                               ptr(err), ptr(qweight), ptr(qzeros), ptr(scales), _stream(work)),
           "awq_gptq_round_block")
+
+
+def gptq_factor(H: torch.Tensor, damp: float):
+    """awq_gptq_factor: H (fp32 [K, K], device, contiguous) becomes, in place, the upper factor U
+    with (H + damp mean(diag H) I)^-1 = U^T U.  -> (U, status): U is H itself; status is a device
+    int32 [1], 0 or 1 + the first refused pivot's column (reading it is the caller's one sync)."""
+    if H.dtype != torch.float32 or H.dim() != 2 or H.shape[0] != H.shape[1] or not H.is_contiguous() or not H.is_cuda:
+        raise ValueError("awq_gptq_factor: H must be a contiguous float32 [K, K] on the device")
+    K = H.shape[0]
+    lib = load_library()
+    nbytes = int(lib.awq_gptq_factor_workspace(K))
+    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=H.device)
+    status = torch.empty(1, dtype=torch.int32, device=H.device)
+    check(lib.awq_gptq_factor(ptr(H), K, float(damp), ptr(work), nbytes, ptr(status), _stream(H)), "awq_gptq_factor")
+    return H, status
 
 
 def dequantize(tensor_q, scales, zeros, rows, K, L, out) -> None:

@@ -28,7 +28,7 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
     place of the source's), the configs, and awq_scales.safetensors: every block's "scales".
     act_samples (--search_loss output, --clip_loss output, --rounding gptq): "<block prefix>.<group>.samples"
     -> token samples; each block's four tensors go to quantize_block, with loss="output" and / or
-    clip_loss="output"; --rounding gptq sets the quantizer's rounding / gptq_damp and logs every weight's
+    clip_loss="output"; --rounding gptq sets the quantizer's rounding / gptq_damp / gptq_factor and logs every weight's
     output error, round-to-nearest -> compensated."""
     from safetensors.torch import save_file
     from .quantization.act_search import quantize_block
@@ -45,6 +45,7 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
     gptq = getattr(args, "rounding", "nearest") == "gptq" and act_samples is not None
     if gptq:    # settings of the quantizer, as clip_loss is: quantize_block's signature is pinned
         quantizer.rounding, quantizer.gptq_damp = "gptq", args.gptq_damp
+        quantizer.gptq_factor = getattr(args, "gptq_factor", "torch")
     clip_kw = {"clip": True, **cfg.act_clip} if cfg.act_clip else {}
     output_loss = act_samples is not None and args.search_loss == "output"
     output_clip = act_samples is not None and bool(cfg.act_clip) and args.clip_loss == "output"

@@ -65,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "--calib_ids forward) after the scale search; not with --act_clip")
     p.add_argument("--gptq_damp", type=float, default=0.01,
                    help="--rounding gptq: the fraction of the Hessian's mean diagonal added to its diagonal")
+    p.add_argument("--gptq_factor", type=str, default="torch", choices=["torch", "hip"],
+                   help="--rounding gptq: who factors the Hessian. torch: three torch.linalg calls; "
+                        "hip: the library's awq_gptq_factor (one reverse Cholesky and a triangular inverse)")
     p.add_argument("--per_channel", action="store_true", help="Use per-channel quantization")
     p.add_argument("--device", type=str, default="cuda" if torch.cuda.is_available() else "cpu",
                    help="Device to use for quantization (cuda, cuda:0, cuda:1, cpu, or 'all' for all GPUs)")
@@ -177,6 +180,8 @@ def check_flags(args) -> Optional[str]:
             return "--rounding gptq refuses --act_clip: the solver moves the ranges the clip search chose"
         if not 0.0 < getattr(args, "gptq_damp", 0.01) < 1.0:
             return "--gptq_damp must be in (0, 1)"
+    elif getattr(args, "gptq_factor", "torch") != "torch":
+        return "--gptq_factor is read by --rounding gptq"
     return None
 
 

@@ -59,6 +59,9 @@ class AWQQuantizer:
     # moves the ranges the clip chose).  Settings of the quantizer, like clip_loss.
     rounding = "nearest"
     gptq_damp = 0.01
+    # quantize_gptq: who factors the damped Hessian.  "torch": cholesky, cholesky_inverse, cholesky
+    # (torch.linalg); "hip": awq_gptq_factor (include/awq_hip.h).
+    gptq_factor = "torch"
 
     def __init__(
         self,

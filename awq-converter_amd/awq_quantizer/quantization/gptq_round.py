@@ -7,9 +7,10 @@ the samples X shrinks.  With H^-1 = U^T U (U upper triangular) column c's error
 e = (w_c - dq_c) / U[c][c] moves every later column j by -e U[c][j].
 
 The dependent chain inside a block of 128 columns is one HIP kernel (include/awq_hip.h
-awq_gptq_round_block: a lane per row, the block in registers); the Cholesky factorisations and the
-update of the columns right of each block are torch.linalg / torch GEMMs on the device, as the
-calibration forward's GEMMs are.  Group parameters are taken when the solver reaches a group's
+awq_gptq_round_block: a lane per row, the block in registers); the update of the columns right of
+each block is a torch GEMM on the device, as the calibration forward's GEMMs are.  The factor U is
+torch.linalg's (three calls) or, with q.gptq_factor = "hip", the library's awq_gptq_factor (one
+reverse Cholesky and a triangular inverse on fp32 MFMA).  Group parameters are taken when the solver reaches a group's
 first column, from the working values as they then stand (static groups, no act-order: g_idx stays
 k // group_size).  The samples are those of the full-precision forward, as AWQ's are, not the
 outputs of already quantized predecessors, as AutoGPTQ's are.
@@ -28,11 +29,21 @@ GPTQ_GROUP_SIZES = (32, 64, 128)
 DAMP_TRIES = 3
 
 
-def _factor(H: torch.Tensor, damp: float) -> Optional[torch.Tensor]:
+GPTQ_FACTORS = ("torch", "hip")
+
+
+def _factor(H: torch.Tensor, damp: float, how: str = "torch") -> Optional[torch.Tensor]:
     """U (fp32, upper, contiguous) with (H + damp mean(diag H) I)^-1 = U^T U, or None when a
-    factorisation fails or leaves a non-finite value."""
+    factorisation fails or leaves a non-finite value.  how: "torch" (three torch.linalg calls) or
+    "hip" (awq_gptq_factor on a copy of H; reading its status is the route's one sync)."""
     K = H.shape[0]
     Hd = H.clone()
+    if how == "hip":
+        # the entry takes damp in (0, 1): a retry that reaches 1 runs with the largest fp32 below it
+        U, status = _hip.gptq_factor(Hd, min(damp, 1.0 - 2.0 ** -24))
+        if int(status) != 0 or not bool(torch.isfinite(U).all()):
+            return None
+        return U
     Hd.diagonal().add_(damp * float(H.diagonal().mean()))
     try:
         L = torch.linalg.cholesky(Hd)
@@ -68,6 +79,9 @@ def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = Non
         raise ValueError(f"hessian must be [{K}, {K}]")
     if isinstance(damp, bool) or not isinstance(damp, (int, float)) or not math.isfinite(damp) or not 0 < damp < 1:
         raise ValueError(f"damp must be a number in (0, 1): {damp!r}")
+    how = getattr(q, "gptq_factor", "torch")
+    if how not in GPTQ_FACTORS:
+        raise ValueError(f"gptq_factor must be one of {GPTQ_FACTORS}: {how!r}")
     if input_scale is not None and (not isinstance(input_scale, torch.Tensor) or input_scale.numel() != K):
         raise ValueError(f"input_scale must have in_features = {K} elements")
 
@@ -106,7 +120,7 @@ def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = Non
     def fallback(why: str, used: float):
         q.logger.warning(f"quantize_gptq: {why}: rounding to nearest")
         return dict(rtn, rounding={"loss": loss_rtn, "loss_rtn": loss_rtn, "dead_columns": n_dead, "damp": used,
-                                   "fallback": True}, **({"input_scale": s} if s is not None else {}))
+                                   "fallback": True, "factor": how}, **({"input_scale": s} if s is not None else {}))
 
     if not bool(torch.isfinite(ws).all()) or not bool(torch.isfinite(H).all()):
         return fallback("a non-finite weight or Hessian", float(damp))
@@ -117,7 +131,7 @@ def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = Non
     work[:, dead] = 0.0
     U, used = None, float(damp)
     for attempt in range(DAMP_TRIES):
-        U = _factor(H, used)
+        U = _factor(H, used, how)
         if U is not None:
             break
         if attempt + 1 < DAMP_TRIES:
@@ -137,5 +151,5 @@ def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = Non
     if s is not None:
         r["input_scale"] = s
     r["rounding"] = {"loss": output_loss(r), "loss_rtn": loss_rtn, "dead_columns": n_dead, "damp": used,
-                     "fallback": False}
+                     "fallback": False, "factor": how}
     return r

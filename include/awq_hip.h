@@ -338,6 +338,38 @@ int awq_gptq_round_block(float* work, int64_t N, int64_t K, int64_t group_size, 
                          const float* u, int64_t col_begin, int64_t n_cols, float* err, int32_t* qweight,
                          int32_t* qzeros, uint16_t* scales, void* stream);
 
+/* ---- GPTQ's factor of the inverse Hessian (additive to ABI 17; no reference counterpart; DESIGN.md
+ * §5.19) ----
+ * h is the fp32 row-major [K, K] Hessian X^T X, symmetric; only its upper triangle (diagonal
+ * included) is read.  In place, h becomes U: upper triangular with a positive diagonal, the strict
+ * lower triangle written as exact zeros, and (H_d)^-1 = U^T U for
+ *   H_d = H', H'[c][c] += (float)(damp * mean(diag H')), H' = H with every diagonal entry equal to 0
+ *   (a dead column) set to 1.
+ * The mean is a device sum in double in a fixed order, so a call's bits do not depend on where its
+ * buffers lie: the 128 entries of a diagonal block by the tree lane l += lane l + 64, + 32, ... + 1,
+ * then the block sums, lane l taking blocks l, l + 128, ... in ascending order, by the same tree;
+ * divided by K.  It need not give the bits of torch's mean().
+ * U is R^-1 for the UPPER triangular R with H_d = R R^T (a Cholesky run from the last column to the
+ * first), which by uniqueness is the factor cholesky(cholesky_inverse(cholesky(H_d)), upper) gives, at
+ * half its arithmetic.  fp32 operands and accumulation throughout (v_mfma_f32_32x32x2_f32).
+ * *status (device int32, an ordinary store) is 0 on success, otherwise 1 + the first column, in
+ * elimination order (K - 1 first), whose pivot was not a finite positive number; h's content is then
+ * unspecified.  Every launched kernel runs to completion in either case: a refused pivot is replaced
+ * by 1, no workgroup waits for another, and the order between phases is the stream's order of
+ * launches.
+ * workspace: awq_gptq_factor_workspace(K) bytes, 8-B aligned: one double per diagonal block of 128
+ * (the block sums); the factorisation and the inversion themselves are in place.
+ * Checked in this order, nothing launched on a failure: K < 0 (AWQ_EINVAL); damp not a finite number
+ * in (0, 1) (AWQ_EINVAL); K == 0: AWQ_OK, no pointer is looked at; K >= 2^31 or K^2 >= 2^42
+ * (AWQ_EUNSUPPORTED); K % 32 != 0 (AWQ_EUNSUPPORTED: 16-B accesses, and the solver's K is a multiple
+ * of its group size); a NULL h, workspace or status; h not 16-B aligned, workspace not 8-B, status not
+ * 4-B; workspace_bytes below awq_gptq_factor_workspace(K) (AWQ_EINVAL).
+ * Caller-owned device memory on the caller's stream; no allocation, no sync. */
+int awq_gptq_factor(float* h, int64_t K, float damp, float* workspace, int64_t workspace_bytes, int32_t* status,
+                    void* stream);
+/* bytes of awq_gptq_factor's workspace: 8 ceil(K / 128); 0 for K <= 0.  No GPU needed. */
+int64_t awq_gptq_factor_workspace(int64_t K);
+
 /* Measurement helper: copy `bytes` (multiple of 16, 16-B aligned buffers) with the
  * quantizer's memory structure (one wave per 4 KiB, 16-B nt loads/stores); bench.py
  * quotes the kernel against this copy's rate. */

@@ -12,7 +12,11 @@ awq_gptq_round_block, csrc/awq_gptq_round.hip) on bf16 weights
   * torch loop: the same in-block loop spelled with torch ops on the GPU (per column: quotient,
     round, clamp, dequantize, error, rank-1 update of the block's later columns; group parameters
     by min / max at each group's first column), timed over --torch-blocks blocks and scaled to
-    K / 128 blocks.  kernel_over_torch_loop is the ratio of the two per-block times.
+    K / 128 blocks.  kernel_over_torch_loop is the ratio of the two per-block times;
+  * factor: the three torch.linalg calls and awq_gptq_factor (csrc/awq_gptq_factor.hip; DESIGN.md
+    §5.19) on the same damped H, alternated in this process after the warm-up, device events around
+    each (median and min - max of --rounds), and the wall time of a whole quantize_gptq call under
+    the two settings of q.gptq_factor, alternated too (wall_*_ms: median, min, max of --rounds).
 
   python scripts/gptq_round_bench.py [--rounds 5] [--tokens 512] [--torch-blocks 4] [--log FILE]
 """
@@ -27,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "awq-converter_amd")]
 import torch  # noqa: E402
 
-SHAPES = {"4096x4096": (4096, 4096), "4096x14336": (4096, 14336)}
+SHAPES = {"4096x4096": (4096, 4096), "4096x8192": (4096, 8192), "4096x14336": (4096, 14336)}
 GS, BITS, BLOCK = 128, 4, 128
 
 
@@ -128,6 +132,24 @@ def main():
         torch_block(work, U, 0, err)                                         # warm
         work.copy_(base)
         t_torch = timed(lambda: [torch_block(work, U, c0, err) for c0, _ in blocks[:nb]]) / nb
+        t_ft, t_fh = [], []
+        _factor(H, 0.01, "hip")                                              # warm (code)
+        for _ in range(args.rounds):
+            t_ft.append(timed(lambda: _factor(H, 0.01)))
+            t_fh.append(timed(lambda: _factor(H, 0.01, "hip")))
+        q.gptq_factor = "hip"
+        q.quantize_gptq(w, x)                                                # warm
+        whole = {"torch": [], "hip": []}                                     # the two settings alternated
+        for _ in range(args.rounds):
+            for how in whole:
+                q.gptq_factor = how
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                r_how = q.quantize_gptq(w, x)
+                torch.cuda.synchronize()
+                whole[how].append((time.perf_counter() - t0) * 1e3)
+            res_hip = r_how
+        q.gptq_factor = "torch"
         med_kernel = statistics.median(t_kernel)
         out = {"weight": name, "N": N, "K": K, "tokens": args.tokens, "group_size": GS, "bits": BITS, "blocks": len(blocks),
                "kernel_ms": round(med_kernel, 3), "kernel_min_ms": round(min(t_kernel), 3),
@@ -136,11 +158,17 @@ def main():
                "quantize_gptq_wall_ms": round(statistics.median(t_whole), 1),
                "torch_loop_us_per_block": round(t_torch * 1e3, 1), "torch_loop_ms_scaled": round(t_torch * len(blocks), 1),
                "kernel_over_torch_loop": round(med_kernel / len(blocks) / t_torch, 5),
-               "loss_over_loss_rtn": round(res["rounding"]["loss"] / res["rounding"]["loss_rtn"], 4)}
+               "loss_over_loss_rtn": round(res["rounding"]["loss"] / res["rounding"]["loss_rtn"], 4),
+               "factor_torch_ms": round(statistics.median(t_ft), 2), "factor_torch_min_ms": round(min(t_ft), 2),
+               "factor_torch_max_ms": round(max(t_ft), 2), "factor_hip_ms": round(statistics.median(t_fh), 2),
+               "factor_hip_min_ms": round(min(t_fh), 2), "factor_hip_max_ms": round(max(t_fh), 2),
+               "wall_torch_ms": [round(f(whole["torch"]), 1) for f in (statistics.median, min, max)],
+               "wall_hip_ms": [round(f(whole["hip"]), 1) for f in (statistics.median, min, max)],
+               "loss_over_loss_rtn_hip": round(res_hip["rounding"]["loss"] / res_hip["rounding"]["loss_rtn"], 4)}
         line = json.dumps(out)
         print(line, flush=True)
         lines.append(line)
-        del H, U, work, base, res
+        del H, U, work, base, res, res_hip
         torch.cuda.empty_cache()
     if args.log:
         os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
