@@ -108,6 +108,10 @@ SIGNATURES = {
     "awq_import_autoawq_gemm": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _P, _P, _P, _P]),
     "awq_export_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "awq_import_gptq": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "awq_gptq_permute_rows": (_I32, [_P, _P, _I64, _I64, _P, _P]),
+    "awq_gptq_gidx_from_perm": (_I32, [_P, _I64, _I64, _P, _P, _P]),
+    "awq_gptq_check_index": (_I32, [_P, _I64, _I64, _P, _P]),
+    "awq_dequantize_gptq": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _I32, _P, _I32, _P]),
     "awq_gptq_round_block": (_I32, [_P, _I64, _I64, _I64, _I32, _I32, _P, _I64, _I64, _P, _P, _P, _P, _P]),
     "awq_gptq_factor": (_I32, [_P, _I64, ctypes.c_float, _P, _I64, _P, _P]),
     "awq_gptq_factor_workspace": (_I64, [_I64]),
@@ -459,6 +463,60 @@ def import_gptq(qweight_t, qzeros_t, scales_t, N: int, K: int, L: int, bits: int
                                         zero_offset, ptr(qweight), ptr(qzeros), ptr(scales),
                                         ctypes.c_void_p(stream_ptr(dev)))
     check(rc, "awq_import_gptq")
+
+
+def _i32_vector(t: torch.Tensor, n: int, what: str) -> None:
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"{what} must be a contiguous int32 [{n}] on the device")
+
+
+def gptq_permute_rows(qweight_t: torch.Tensor, src: torch.Tensor, out: torch.Tensor) -> None:
+    """awq_gptq_permute_rows: out [K/8, N] = the nibble rows src of qweight_t [K/8, N] (nibble row k of
+    out is nibble row src[k] of qweight_t); an entry of src outside [0, K) takes row 0."""
+    R, N = qweight_t.shape
+    for t in (qweight_t, out):
+        if t.dtype != torch.int32 or tuple(t.shape) != (R, N) or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"awq_gptq_permute_rows: qweight must be a contiguous int32 [{R}, {N}] on the device")
+    _i32_vector(src, 8 * R, "awq_gptq_permute_rows: src")
+    check(load_library().awq_gptq_permute_rows(ptr(qweight_t), ptr(src), N, 8 * R, ptr(out), _stream(out)),
+          "awq_gptq_permute_rows")
+
+
+def gptq_gidx_from_perm(perm: torch.Tensor, L: int, g_idx=None, invperm=None) -> None:
+    """awq_gptq_gidx_from_perm: g_idx[perm[i]] = i // L, invperm[perm[i]] = i (either may be None)."""
+    K = perm.numel()
+    _i32_vector(perm, K, "awq_gptq_gidx_from_perm: perm")
+    for t in (g_idx, invperm):
+        if t is not None:
+            _i32_vector(t, K, "awq_gptq_gidx_from_perm: an output")
+    check(load_library().awq_gptq_gidx_from_perm(ptr(perm), K, L, ptr(g_idx), ptr(invperm), _stream(perm)),
+          "awq_gptq_gidx_from_perm")
+
+
+def gptq_check_index(idx: torch.Tensor, bound: int) -> torch.Tensor:
+    """awq_gptq_check_index -> status, a device int32 [1]: 0, or 1 + the first i with idx[i] outside
+    [0, bound) (reading it is the caller's sync)."""
+    _i32_vector(idx, idx.numel(), "awq_gptq_check_index: idx")
+    status = torch.empty(1, dtype=torch.int32, device=idx.device)
+    check(load_library().awq_gptq_check_index(ptr(idx), idx.numel(), bound, ptr(status), _stream(idx)),
+          "awq_gptq_check_index")
+    return status
+
+
+def dequantize_gptq(qweight_t, qzeros_t, scales_t, g_idx, zero_offset: int, out: torch.Tensor) -> None:
+    """awq_dequantize_gptq: out [N, K] (fp32 / fp16 / bf16) from a GPTQ-layout linear with any g_idx
+    in [0, G), G = scales_t's rows."""
+    N, K = out.shape
+    G = scales_t.shape[0]
+    for t, dt, shape, what in ((qweight_t, torch.int32, (K // 8, N), "qweight"), (qzeros_t, torch.int32, (G, N // 8), "qzeros"),
+                               (scales_t, torch.float16, (G, N), "scales"), (g_idx, torch.int32, (K,), "g_idx")):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != out.device:
+            raise ValueError(f"awq_dequantize_gptq: {what} must be a contiguous {dt} {shape} on {out.device}")
+    if out.dtype not in (torch.float32, torch.float16, torch.bfloat16) or not out.is_contiguous():
+        raise ValueError("awq_dequantize_gptq: out must be a contiguous fp32 / fp16 / bf16 [N, K]")
+    check(load_library().awq_dequantize_gptq(ptr(qweight_t), ptr(qzeros_t), ptr(scales_t), ptr(g_idx), N, K, G,
+                                             zero_offset, ptr(out), AWQ_DTYPE[out.dtype], _stream(out)),
+          "awq_dequantize_gptq")
 
 
 GPTQ_BLOCK = 128         # columns per awq_gptq_round_block call at most (include/awq_hip.h)

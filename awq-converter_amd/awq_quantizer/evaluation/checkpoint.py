@@ -9,11 +9,12 @@ runs the quantized model exactly as it runs the source.
       triple is dequantized, every other tensor is read as written.  A --fold_scales directory is
       used as it stands: folded norms, biases and rows with scaled-domain weights;
   gptq (the same files + quantize_config.json with quant_method "gptq"): the same, every linear
-      imported through awq_import_gptq (g_idx is checked to be k // group_size and not read again).
+      imported through awq_import_gptq when its g_idx is k // group_size, and dequantized in one
+      pass by awq_dequantize_gptq when it is not (act-order, desc_act true).
 
 Tensors the directory does not hold come from the source.  `dequant` does the arithmetic:
 DeviceDequant runs the library's kernels (awq_dequantize, awq_dequantize_packed,
-awq_import_autoawq_gemm, awq_import_gptq); host tests inject a stub.
+awq_import_autoawq_gemm, awq_import_gptq, awq_dequantize_gptq); host tests inject a stub.
 """
 from __future__ import annotations
 

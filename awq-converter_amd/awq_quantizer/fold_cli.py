@@ -46,6 +46,7 @@ def _main_fold_scales(args, cfg: StreamSettings, loader, index: List[TensorInfo]
     if gptq:    # settings of the quantizer, as clip_loss is: quantize_block's signature is pinned
         quantizer.rounding, quantizer.gptq_damp = "gptq", args.gptq_damp
         quantizer.gptq_factor = getattr(args, "gptq_factor", "torch")
+        quantizer.gptq_act_order = bool(getattr(args, "gptq_act_order", False))
     clip_kw = {"clip": True, **cfg.act_clip} if cfg.act_clip else {}
     output_loss = act_samples is not None and args.search_loss == "output"
     output_clip = act_samples is not None and bool(cfg.act_clip) and args.clip_loss == "output"

@@ -68,6 +68,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gptq_factor", type=str, default="torch", choices=["torch", "hip"],
                    help="--rounding gptq: who factors the Hessian. torch: three torch.linalg calls; "
                         "hip: the library's awq_gptq_factor (one reverse Cholesky and a triangular inverse)")
+    p.add_argument("--gptq_act_order", action="store_true",
+                   help="--rounding gptq with --output_format gptq: round the input columns in order of decreasing "
+                        "diag(H) and form the groups in that order (GPTQ's desc_act; the checkpoint's g_idx says "
+                        "which group a column is in)")
     p.add_argument("--per_channel", action="store_true", help="Use per-channel quantization")
     p.add_argument("--device", type=str, default="cuda" if torch.cuda.is_available() else "cpu",
                    help="Device to use for quantization (cuda, cuda:0, cuda:1, cpu, or 'all' for all GPUs)")
@@ -134,9 +138,16 @@ GPTQ_ONE_PROCESS = "--output_format gptq runs in one process (it is not written 
 CHECKPOINT_FORMATS = ("autoawq", "gptq")
 
 
+ACT_ORDER_NEEDS = ("--gptq_act_order needs --rounding gptq and --output_format gptq (act-order is the solver's column "
+                   "order, and only the GPTQ layout has a g_idx to record it)")
+
+
 def check_flags(args) -> Optional[str]:
     """The rules that need nothing but the flags: main() applies them before it touches a
     device or the model.  The first error's message, or None."""
+    if getattr(args, "gptq_act_order", False) and (getattr(args, "rounding", "nearest") != "gptq"
+                                                   or args.output_format != "gptq"):
+        return ACT_ORDER_NEEDS
     if args.calib_ids and args.act_stats:
         return "--calib_ids and --act_stats are mutually exclusive: the statistics come from one of them"
     if args.fold_scales and (args.scale_method != "awq" or not has_stats(args)

@@ -351,7 +351,7 @@ def write_gptq_configs(output_dir: str, args, loader, not_converted: List[str], 
     "gptq" stores as 15 (loaders differ on masking after they add 1): warned about per tensor and
     recorded under "zero_points_at_0"."""
     qcfg = {"quant_method": "gptq", "bits": 4, "group_size": args.group_size, "sym": bool(args.symmetric),
-            "desc_act": False, "checkpoint_format": args.gptq_format}
+            "desc_act": bool(getattr(args, "gptq_act_order", False)), "checkpoint_format": args.gptq_format}
     if not_converted:
         qcfg["modules_to_not_convert"] = list(not_converted)
     zeros_at_0 = {k: int(v) for k, v in zeros_at_0.items() if int(v)}

@@ -194,7 +194,8 @@ def quantize_layer_group(q, weights: Dict[str, torch.Tensor], activations: Optio
     for name in weights:
         w = sr["weights"][name]
         if gptq_samples is not None:              # the solver scales the weight and the samples itself
-            r = q.quantize_gptq(w, gptq_samples, input_scale=s, damp=getattr(q, "gptq_damp", 0.01))
+            r = q.quantize_gptq(w, gptq_samples, input_scale=s, damp=getattr(q, "gptq_damp", 0.01),
+                                act_order=bool(getattr(q, "gptq_act_order", False)))
             _log_rounding(q, name, r)
         elif packed:
             r = _quantize_scaled(q, w, s, one_pass, scaled=scaled.get(name))
@@ -379,7 +380,8 @@ def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[t
                 if smp is None:
                     results[m] = q.quantize_packed(w)
                     continue
-                r = q.quantize_gptq(w, smp, damp=getattr(q, "gptq_damp", 0.01))
+                r = q.quantize_gptq(w, smp, damp=getattr(q, "gptq_damp", 0.01),
+                                    act_order=bool(getattr(q, "gptq_act_order", False)))
                 _log_rounding(q, m, r)
                 report[g.name].setdefault("rounding", {})[m] = r.pop("rounding")
                 results[m] = r

@@ -12,6 +12,9 @@ from ..layout import packed_shapes, read_meta, result_meta, rows_k
 
 def export_autoawq(q, packed: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """A quantize_packed() result of a 2-D weight in the GEMM layout."""
+    if packed.get("perm") is not None:
+        raise ValueError("export_autoawq: an act-order result (it carries 'perm') has no AutoAWQ GEMM form: that "
+                         "layout has no g_idx; use export_gptq")
     shape, = read_meta(packed, "shape")
     if len(shape) != 2:
         raise ValueError(f"AutoAWQ GEMM layout is for 2-D linear weights, got shape {shape}")
@@ -65,6 +68,9 @@ def dequantize_autoawq(q, gemm: Dict[str, torch.Tensor], group_size: Optional[in
 
 def dequantize_packed(q, packed: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Inverse of quantize_packed with the reference's dequantize arithmetic (fp16 math)."""
+    if packed.get("perm") is not None:      # permuted columns: through the GPTQ layout, whose g_idx undoes the order
+        return q.dequantize_gptq(q.export_gptq(packed, "gptq_v2"), *read_meta(packed, "group_size", "symmetric"),
+                                 "gptq_v2", dtype)
     shape, L, bits, sym = read_meta(packed, "shape", "group_size", "bits", "symmetric")
     rows, K = rows_k(shape)
     out = torch.empty(shape, dtype=torch.float32, device=packed["qweight"].device)

@@ -62,6 +62,9 @@ class AWQQuantizer:
     # quantize_gptq: who factors the damped Hessian.  "torch": cholesky, cholesky_inverse, cholesky
     # (torch.linalg); "hip": awq_gptq_factor (include/awq_hip.h).
     gptq_factor = "torch"
+    # quantize_layer_group / quantize_block with rounding = "gptq": GPTQ's act-order (desc_act), the
+    # columns rounded in order of decreasing diag(H) (quantize_gptq's act_order)
+    gptq_act_order = False
 
     def __init__(
         self,
@@ -515,7 +518,11 @@ class AWQQuantizer:
         [in/group_size, out], g_idx int32 [in] = k // group_size; sequential nibbles, no
         interleave.  Symmetric results keep their fields (q + 8, zero 8).  checkpoint_format
         "gptq" (v1) stores zero - 1 modulo 16, "gptq_v2" the zero itself; "zero_points_at_0"
-        (int64 0-d, on the device) counts the zero points v1 stores as 15.  Device tensors."""
+        (int64 0-d, on the device) counts the zero points v1 stores as 15.  Device tensors.
+        A result that carries "perm" (quantize_gptq(act_order=True), import_gptq of an act-order
+        linear) is written in the act-order layout, desc_act = true: qweight's fields back in the
+        original column order (awq_gptq_permute_rows), g_idx[perm[i]] = i // group_size, qzeros
+        and scales those of the permuted groups."""
         from .gptq import export_gptq
         if isinstance(packed, torch.Tensor):
             packed = self.quantize_packed(packed)
@@ -524,28 +531,41 @@ class AWQQuantizer:
     def import_gptq(self, gptq: Dict[str, torch.Tensor], group_size: Optional[int] = None,
                     symmetric: Optional[bool] = None, checkpoint_format: str = "gptq") -> Dict[str, torch.Tensor]:
         """The inverse of export_gptq (include/awq_hip.h awq_import_gptq): `gptq` holds qweight,
-        qzeros and scales of one linear in the GPTQ layout (and optionally g_idx, which must be
-        k // group_size: act-order is not supported), on the CPU or the device.  Returns a
-        quantize_packed()-shaped dict on the device, as import_autoawq does.  ValueError for
-        inconsistent shapes, an unknown checkpoint_format or an act-order g_idx; RuntimeError for
-        what the C call refuses."""
+        qzeros and scales of one linear in the GPTQ layout (and optionally g_idx), on the CPU or the
+        device.  Returns a quantize_packed()-shaped dict on the device, as import_autoawq does.  A
+        g_idx other than k // group_size in which every group has exactly group_size entries is an
+        act-order linear: the result is in permuted column order and carries "perm", the stable
+        ascending argsort of g_idx.  ValueError for inconsistent shapes, an unknown
+        checkpoint_format or any other g_idx; RuntimeError for what the C call refuses."""
         from .gptq import import_gptq
         return import_gptq(self, gptq, group_size, symmetric, checkpoint_format)
 
     def dequantize_gptq(self, gptq: Dict[str, torch.Tensor], group_size: Optional[int] = None,
                         symmetric: Optional[bool] = None, checkpoint_format: str = "gptq",
                         dtype: torch.dtype = torch.float32) -> torch.Tensor:
-        """import_gptq, then dequantize_packed: the [out, in] weight a GPTQ-layout linear holds."""
+        """The [out, in] weight a GPTQ-layout linear holds: import_gptq, then dequantize_packed; a
+        linear whose g_idx is not k // group_size, balanced or not (any values in [0, in/group_size)),
+        takes the fused awq_dequantize_gptq straight to `dtype`."""
         from .gptq import dequantize_gptq
         return dequantize_gptq(self, gptq, group_size, symmetric, checkpoint_format, dtype)
 
     def quantize_gptq(self, tensor: torch.Tensor, samples: Optional[torch.Tensor] = None, *,
                       hessian: Optional[torch.Tensor] = None, input_scale: Optional[torch.Tensor] = None,
-                      damp: float = 0.01) -> Dict[str, torch.Tensor]:
+                      damp: float = 0.01, act_order: bool = False) -> Dict[str, torch.Tensor]:
         """quantize_packed with GPTQ's error-compensated rounding instead of round-to-nearest
         (gptq_round.py; include/awq_hip.h awq_gptq_round_block): a 2-D
         [out_features, in_features] bf16 / fp16 / fp32 weight, group_size 32 / 64 / 128 dividing
-        in_features, static groups (no act-order).
+        in_features, static groups.
+
+        act_order=True (GPTQ's desc_act): after the dead-column fix, perm =
+        argsort(diag(H), descending, stable), and the same solve runs on W[:, perm] and
+        H[perm][:, perm]; groups are formed in that order.  The result's packed tensors are then
+        in PERMUTED column order and it carries "perm" (int32 [in_features] on the device; perm[i]
+        = the original column at position i) and rounding["act_order"] = True; "input_scale" stays
+        in the original order.  export_gptq writes such a dict in the act-order layout,
+        dequantize_packed returns the original column order, quantization_error permutes its
+        tensor and samples alike, and export_autoawq refuses it (that layout has no g_idx).  The
+        fallback result is plain round-to-nearest, in storage order, without "perm".
 
         samples [tokens, in_features]: token samples of the linear's input; H = X^T X is formed
         from them in fp32 on the device.  hessian [in, in] replaces it (samples are then only
@@ -563,7 +583,8 @@ class AWQQuantizer:
         multiplies damp by 10, three tries in all; after that, and for a non-finite weight or
         Hessian, the result is quantize_packed's, with a warning and fallback = True."""
         from .gptq_round import quantize_gptq
-        return quantize_gptq(self, tensor, samples, hessian=hessian, input_scale=input_scale, damp=damp)
+        return quantize_gptq(self, tensor, samples, hessian=hessian, input_scale=input_scale, damp=damp,
+                             act_order=act_order)
 
     def dequantize_packed(self, packed: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """Inverse of quantize_packed with the reference's dequantize arithmetic (fp16 math)."""

@@ -11,8 +11,10 @@ awq_gptq_round_block: a lane per row, the block in registers); the update of the
 each block is a torch GEMM on the device, as the calibration forward's GEMMs are.  The factor U is
 torch.linalg's (three calls) or, with q.gptq_factor = "hip", the library's awq_gptq_factor (one
 reverse Cholesky and a triangular inverse on fp32 MFMA).  Group parameters are taken when the solver reaches a group's
-first column, from the working values as they then stand (static groups, no act-order: g_idx stays
-k // group_size).  The samples are those of the full-precision forward, as AWQ's are, not the
+first column, from the working values as they then stand (static groups).  act_order=True is the
+same solve on W[:, perm] and H[perm][:, perm], perm the columns by decreasing diag(H) (GPTQ's
+desc_act): the result is then in permuted column order and carries "perm", and
+export_gptq records the groups in g_idx; otherwise g_idx stays k // group_size.  The samples are those of the full-precision forward, as AWQ's are, not the
 outputs of already quantized predecessors, as AutoGPTQ's are.
 """
 from __future__ import annotations
@@ -57,7 +59,7 @@ def _factor(H: torch.Tensor, damp: float, how: str = "torch") -> Optional[torch.
 
 def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = None, *,
                   hessian: Optional[torch.Tensor] = None, input_scale: Optional[torch.Tensor] = None,
-                  damp: float = 0.01) -> Dict[str, torch.Tensor]:
+                  damp: float = 0.01, act_order: bool = False) -> Dict[str, torch.Tensor]:
     """AWQQuantizer.quantize_gptq (its docstring says what goes in and out)."""
     q._check_input(tensor)
     q._check_mode()
@@ -97,10 +99,16 @@ def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = Non
     if samples is not None:
         xs = device_input(samples.detach().to(w.dtype), dev)       # what awq_output_error reads: the unscaled inputs
 
-    def output_loss(r) -> Optional[float]:
+    def output_loss(r, perm=None) -> Optional[float]:
+        """The output error of r on the samples; perm: r's columns are w's, xs' and s' in this order
+        (the error is invariant under a joint permutation of the columns)."""
         if xs is None:
             return None
-        err_sq, _, _ = _hip.output_error(w, L, q.bits, q.symmetric, r["qweight"], r["qzeros"], r["scales"], xs, s,
+        wv, xv, sv = w, xs, s
+        if perm is not None:
+            wv, xv = w.index_select(1, perm).contiguous(), xs.index_select(1, perm).contiguous()
+            sv = s.index_select(0, perm).contiguous() if s is not None else None
+        err_sq, _, _ = _hip.output_error(wv, L, q.bits, q.symmetric, r["qweight"], r["qzeros"], r["scales"], xv, sv,
                                          ref=False)
         return float(err_sq.double().sum())
 
@@ -129,6 +137,11 @@ def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = Non
     if work.data_ptr() == ws.data_ptr():          # fp32 weights: the caller's tensor is not the working copy
         work = work.clone()
     work[:, dead] = 0.0
+    perm = None
+    if act_order:     # the columns that matter most first, while every other column can still absorb their error
+        perm = torch.argsort(H.diagonal(), descending=True, stable=True)
+        H = H.index_select(0, perm).index_select(1, perm).contiguous()
+        work = work.index_select(1, perm).contiguous()
     U, used = None, float(damp)
     for attempt in range(DAMP_TRIES):
         U = _factor(H, used, how)
@@ -150,6 +163,9 @@ def quantize_gptq(q, tensor: torch.Tensor, samples: Optional[torch.Tensor] = Non
             work[:, c1:].addmm_(err, U[c0:c1, c1:], alpha=-1.0)
     if s is not None:
         r["input_scale"] = s
-    r["rounding"] = {"loss": output_loss(r), "loss_rtn": loss_rtn, "dead_columns": n_dead, "damp": used,
+    r["rounding"] = {"loss": output_loss(r, perm), "loss_rtn": loss_rtn, "dead_columns": n_dead, "damp": used,
                      "fallback": False, "factor": how}
+    if perm is not None:
+        r["perm"] = perm.to(torch.int32)
+        r["rounding"]["act_order"] = True
     return r

@@ -34,6 +34,14 @@ def quantization_error(q, tensor: torch.Tensor, result: Dict[str, torch.Tensor],
         raise ValueError(f"quantization_error: samples {tuple(samples.shape)} do not match a 2-D weight "
                          f"[out, {K}] (tensor shape {tuple(tensor.shape)})")
     dev = q.compute_device()
+    if result.get("perm") is not None:      # an act-order result: its columns are the tensor's in this order
+        if tensor.dim() != 2 or result["perm"].numel() != K:
+            raise ValueError(f"quantization_error: perm {tuple(result['perm'].shape)} does not match a 2-D weight "
+                             f"[out, {K}] (tensor shape {tuple(tensor.shape)})")
+        perm = result["perm"].to(dev, torch.int64)
+        tensor = tensor.to(dev).index_select(1, perm)
+        samples = samples.to(dev).index_select(1, perm) if samples is not None else None
+        in_scale = in_scale.to(dev).index_select(0, perm) if in_scale is not None else None
     w = w_orig = device_input(tensor, dev)
     if in_scale is not None:     # the result quantizes W * diag(input_scale): measure against that
         w = _hip.apply_input_scale(w, in_scale.to(dev, torch.float32).contiguous())

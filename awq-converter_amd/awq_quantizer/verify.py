@@ -22,9 +22,11 @@ awq_scales.safetensors when --fold_scales wrote one: first fold_rows(W, <layer>.
 then input_scale = <layer>.weight.input_scale (quantize_block's order); entries gain "row_folded"
 and "layout": "autoawq".  --output_format gptq directories (the same files, with
 quantize_config.json saying quant_method "gptq") take the same audit through
-AWQQuantizer.import_gptq ("layout": "gptq"); a g_idx that is not k // group_size (act-order is
-not supported), a symmetric checkpoint with a stored zero other than 8, and a missing or unknown
-checkpoint_format are findings.  With a sidecar the fold itself is audited (fold_audit): one input scale
+AWQQuantizer.import_gptq ("layout": "gptq"); with desc_act true in the settings a linear whose
+g_idx is balanced (group_size entries in every group) is imported in its act-order and measured
+against the source weight permuted alike (the samples of --act_samples too).  A g_idx that is not
+k // group_size without desc_act, an unbalanced one with it, a symmetric checkpoint with a stored
+zero other than 8, and a missing or unknown checkpoint_format are findings.  With a sidecar the fold itself is audited (fold_audit): one input scale
 per layer group, the folded norm weights and producer biases bit for bit.  Every other tensor must
 equal the source's bytes (report key "copied").  Any finding is a "problems" entry and makes the
 return code 1.  Checkpoints written by AutoAWQ itself are out of scope (parity unpinned).
@@ -360,8 +362,6 @@ def read_gptq_config(quantized_dir: str) -> Tuple[dict, Dict[str, str]]:
     gs = cfg.get("group_size")
     if not isinstance(gs, int) or isinstance(gs, bool) or gs <= 0:
         problems["quantize_config.json"] = f"group_size {gs!r} is not a positive integer"
-    if cfg.get("desc_act"):
-        problems["quantize_config.json"] = "desc_act is true: act-order checkpoints are not supported"
     fmt = cfg.get("checkpoint_format")
     if fmt not in GPTQ_FORMATS:
         problems["quantize_config.json"] = (f"checkpoint_format {fmt!r} is missing or unknown (known: "
@@ -371,9 +371,16 @@ def read_gptq_config(quantized_dir: str) -> Tuple[dict, Dict[str, str]]:
     return out, problems
 
 
-def gptq_findings(gptq: Dict[str, torch.Tensor], group_size: int, symmetric: bool, checkpoint_format: str) -> List[str]:
+def gptq_desc_act(quantized_dir: str) -> bool:
+    """The settings of a GPTQ directory say desc_act true: its linears may carry an act-order g_idx."""
+    return bool((_gptq_settings(quantized_dir) or {}).get("desc_act"))
+
+
+def gptq_findings(gptq: Dict[str, torch.Tensor], group_size: int, symmetric: bool, checkpoint_format: str,
+                  desc_act: bool = False) -> List[str]:
     """What verify reports of one GPTQ linear before it is imported: a g_idx that is not
-    k // group_size, and, symmetric, a stored zero point other than 8."""
+    k // group_size (with desc_act: one that is neither that nor balanced, group_size entries in
+    every group, which import_gptq reads), and, symmetric, a stored zero point other than 8."""
     out = []
     g = gptq.get("g_idx")
     K = int(gptq["qweight"].shape[0]) * 8
@@ -385,6 +392,10 @@ def gptq_findings(gptq: Dict[str, torch.Tensor], group_size: int, symmetric: boo
             out.append(f"g_idx has {g.numel()} entries for in_features {K}")
         else:
             bad = (g != torch.arange(K, dtype=torch.int64) // group_size).nonzero().reshape(-1)
+            if bad.numel() and desc_act:
+                from .quantization.gptq import act_order_perm
+                if K % group_size == 0 and act_order_perm(g, K, group_size) is not None:
+                    bad = bad[:0]
             if bad.numel():
                 k = int(bad[0])
                 out.append(f"g_idx[{k}] = {int(g[k])}, not {k // group_size} = k // group_size at {bad.numel()} "
@@ -497,6 +508,7 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
     copied: List[str] = []
     gptq = layout == "gptq"
     cfg, problems = read_gptq_config(d) if gptq else read_quant_config(d)
+    desc_act = gptq and gptq_desc_act(d)
 
     def problem(name: str, why: str) -> None:
         problems[name] = why
@@ -551,7 +563,8 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
             try:
                 if gptq:
                     gemm["g_idx"] = read_ckpt(f"{layer}.g_idx")
-                    found = gptq_findings(gemm, cfg["group_size"], cfg["symmetric"], cfg["checkpoint_format"])
+                    found = gptq_findings(gemm, cfg["group_size"], cfg["symmetric"], cfg["checkpoint_format"],
+                                          desc_act)
                     if found:
                         problem(name, "; ".join(found))
                         continue

@@ -301,10 +301,64 @@ int awq_export_gptq(const int32_t* qweight, const int32_t* qzeros, const uint16_
  * word; z' = (zs + zero_offset) & 15, and the unused high fields of a row's last qzeros word
  * (G % 8 != 0) are 0.  The same checks in the same order.  Nothing on the device is refused: a
  * symmetric checkpoint whose stored zero is not 8 imports as it is stored (the Python reader
- * reports it); g_idx is not an input (act-order is not supported). */
+ * reports it); g_idx is not an input: an act-order checkpoint goes through awq_gptq_permute_rows
+ * first (below). */
 int awq_import_gptq(const int32_t* qweight_t, const int32_t* qzeros_t, const uint16_t* scales_t, int64_t N, int64_t K,
                     int64_t group_size, int bits, int symmetric, int zero_offset, int32_t* qweight, int32_t* qzeros,
                     uint16_t* scales, void* stream);
+
+/* ---- GPTQ act-order, desc_act = true (additive to ABI 17; no reference counterpart; DESIGN.md
+ * §5.20) ----
+ * An act-order linear was solved on the columns in the order perm (perm[i] = the original column
+ * rounded i-th); groups are formed in that order, so g_idx[perm[i]] = i / group_size, qzeros_t and
+ * scales_t are those of the permuted problem, and qweight_t holds the fields in the ORIGINAL column
+ * order.  All four entries: caller-owned device memory on the caller's stream, 64-bit offsets, no
+ * allocation, no workspace, no sync; checked in the order given, nothing launched on a failure.
+ *
+ * awq_gptq_permute_rows: a gather of nibble rows on [K/8, N] words: nibble i of output word (r, n)
+ * = nibble src[8r + i] % 8 of input word (src[8r + i] / 8, n).  Export: awq_export_gptq of the
+ * permuted result into a temporary, then this with src = invperm; import: this with src = perm,
+ * then awq_import_gptq.  A src entry outside [0, K) is not read through: it takes field 0
+ * (awq_gptq_check_index reports such entries).  Checks: a negative N or K (AWQ_EINVAL); N % 8 or
+ * K % 8 != 0 (AWQ_EINVAL); N == 0 or K == 0: AWQ_OK, no pointer is looked at; N or K >= 2^31 or
+ * N K > 2^42 (AWQ_EUNSUPPORTED); a NULL pointer; a pointer not 4-B aligned; qweight_t_out ==
+ * qweight_t_in (AWQ_EINVAL: the gather is not in place).  16-B aligned qweight_t_in and
+ * qweight_t_out take 16-B accesses, which give the same bits. */
+int awq_gptq_permute_rows(const int32_t* qweight_t_in, const int32_t* src, int64_t N, int64_t K,
+                          int32_t* qweight_t_out, void* stream);
+
+/* g_idx[perm[i]] = i / group_size and invperm[perm[i]] = i for i < K; either output may be NULL,
+ * not both.  A perm that is not a permutation is the caller's error: an entry outside [0, K)
+ * writes nothing, a repeated one writes one of its values, a missing one leaves its outputs
+ * unwritten.  Checks: K < 0; group_size <= 0 (AWQ_EINVAL); K == 0: AWQ_OK; K >= 2^31
+ * (AWQ_EUNSUPPORTED); perm NULL; both outputs NULL; a pointer not 4-B aligned (AWQ_EINVAL). */
+int awq_gptq_gidx_from_perm(const int32_t* perm, int64_t K, int64_t group_size, int32_t* g_idx, int32_t* invperm,
+                            void* stream);
+
+/* *status (device int32, an ordinary store by one workgroup) = 0 when every idx[i], i < n, lies in
+ * [0, bound), otherwise 1 + the first i that does not: the device-side check of a src, perm or
+ * g_idx before the entries above and below clamp it.  Checks: n or bound < 0 (AWQ_EINVAL); n or
+ * bound >= 2^31 (AWQ_EUNSUPPORTED); status NULL, idx NULL with n > 0; a pointer not 4-B aligned
+ * (AWQ_EINVAL).  n == 0 stores 0. */
+int awq_gptq_check_index(const int32_t* idx, int64_t n, int64_t bound, int32_t* status, void* stream);
+
+/* The [N, K] weight of a GPTQ-layout linear with ANY g_idx, in one pass: out[n, k] =
+ * fp16(fp16(u - z') s) with u = nibble k % 8 of qweight_t (k / 8, n), g = g_idx[k], s = scales_t
+ * (g, n), z' = (nibble n % 8 of qzeros_t (g, n / 8) + zero_offset) & 15: awq_dequantize_packed's
+ * arithmetic (u - z' is exact in fp16; its product with s, exact in fp32, is rounded to fp16 once).
+ * out_dtype AWQ_DTYPE_F32 (the fp16 value widened), AWQ_DTYPE_F16 (its bits) or AWQ_DTYPE_BF16 (the
+ * fp16 value rounded to nearest even; a NaN is 0x7FC0).  A NaN product carries the hardware
+ * conversion's payload, not the reference's (awq_dequantize_packed pins that one).  g_idx need not
+ * be balanced nor a multiple of anything: each entry only has to lie in [0, G), G = the rows of
+ * qzeros_t and scales_t; one outside takes group 0 and is not read through.
+ * Checks: a negative N, K or G (AWQ_EINVAL); N % 8 or K % 8 != 0 (AWQ_EINVAL); zero_offset outside
+ * {0, 1} (AWQ_EINVAL); out_dtype (AWQ_EUNSUPPORTED); N == 0 or K == 0: AWQ_OK, no pointer is looked
+ * at; G == 0 (AWQ_EINVAL); N, K or G >= 2^31 or N K > 2^42 (AWQ_EUNSUPPORTED); a NULL pointer;
+ * words or fp32 not 4-B aligned, 16-bit values not 2-B aligned (AWQ_EINVAL).  An `out` aligned to
+ * two elements takes two-element stores, which give the same bits. */
+int awq_dequantize_gptq(const int32_t* qweight_t, const int32_t* qzeros_t, const uint16_t* scales_t,
+                        const int32_t* g_idx, int64_t N, int64_t K, int64_t G, int zero_offset, void* out,
+                        int out_dtype, void* stream);
 
 /* ---- GPTQ error-compensated rounding, one block of input columns (additive to ABI 17; no reference
  * counterpart) ----
