@@ -160,6 +160,9 @@ SIGNATURES = {
     "awq_rmsnorm_stats": (_I32, [_P, _I32, _I64, _I64, _P, ctypes.c_float, _P, _I64, _P, _P, _P, _P]),
     "awq_swiglu_stats": (_I32, [_P, _P, _I32, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P]),
     "awq_logit_compare": (_I32, [_P, _P, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "awq_hadamard_rows": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _P]),
+    "awq_hadamard_cols": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _P, _P]),
+    "awq_hadamard_cols_work_bytes": (_I64, [_I32, _I64, _I64, _I64, _I32]),
 }
 
 _lib = None
@@ -955,3 +958,35 @@ def fold_rows(w: torch.Tensor, row_scale: torch.Tensor, out: Optional[torch.Tens
     check(load_library().awq_fold_rows(ptr(w), AWQ_DTYPE[w.dtype], rows, K, ptr(row_scale), ptr(out), _stream(w)),
           "awq_fold_rows")
     return out
+
+
+# ---- Hadamard rotation (include/awq_hip.h awq_hadamard_rows / awq_hadamard_cols) ----
+def _hadamard_args(x, pre, mix, out, n):
+    if x.dim() != 2 or not x.is_contiguous() or x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise ValueError("the Hadamard transform takes a contiguous 2-D bf16 / fp16 / fp32 tensor")
+    if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError("out must match the input (shape, dtype, device, contiguous)")
+    for t, size, what in ((pre, n, "pre"), (mix, None, "mix")):
+        if t is not None and (t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous()
+                              or (size is not None and t.numel() != size)):
+            raise ValueError(f"{what} must be a contiguous fp32 tensor on {x.device}" + (f" of {size} elements" if size else ""))
+
+
+def hadamard_rows(x: torch.Tensor, L: int, m: int, pre, mix, out: torch.Tensor) -> None:
+    """awq_hadamard_rows: out [R, K] = every L-segment of every row of x, times pre, through M (x) H."""
+    _hadamard_args(x, pre, mix, out, x.shape[1])
+    R, K = x.shape
+    check(load_library().awq_hadamard_rows(ptr(x), AWQ_DTYPE[x.dtype], R, K, L, m, ptr(pre), ptr(mix), ptr(out),
+                                           _stream(x)), "awq_hadamard_rows")
+
+
+def hadamard_cols(x: torch.Tensor, L: int, m: int, pre, mix, out: torch.Tensor) -> None:
+    """awq_hadamard_cols: the same down the rows of x [K, N]; allocates the fp64 workspace of a
+    16-bit transform that takes more than one pass."""
+    _hadamard_args(x, pre, mix, out, x.shape[0])
+    K, N = x.shape
+    lib = load_library()
+    nbytes = lib.awq_hadamard_cols_work_bytes(AWQ_DTYPE[x.dtype], K, N, L, m)
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device) if nbytes else None
+    check(lib.awq_hadamard_cols(ptr(x), AWQ_DTYPE[x.dtype], K, N, L, m, ptr(pre), ptr(mix), ptr(out), ptr(work),
+                                _stream(x)), "awq_hadamard_cols")

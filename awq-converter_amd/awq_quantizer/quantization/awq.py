@@ -632,6 +632,13 @@ class AWQQuantizer:
         from .report import quantization_error_model
         return quantization_error_model(self, tensors, results)
 
+    def hadamard_transform(self, x: torch.Tensor, dim: int, *, length: Optional[int] = None,
+                           pre: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The orthonormal Hadamard transform of x along dim (0 or -1), in segments of `length`
+        (rotation.hadamard_transform).  x is moved to the compute device."""
+        from ..rotation import hadamard_transform
+        return hadamard_transform(x.to(self.compute_device()), dim, length=length, pre=pre)
+
 
 def _alloc_packed(q: AWQQuantizer, shape, dev: torch.device) -> Dict[str, torch.Tensor]:
     """quantize_packed()'s result dict for an input of `shape`: unwritten outputs on `dev`, and the metadata."""

@@ -993,6 +993,35 @@ int awq_logit_compare(const void* ref, const void* q, int dtype, int64_t T, int6
                       float* nll_ref, float* nll_q, float* kl,
                       int32_t* argmax_ref, int32_t* argmax_q, void* stream);
 
+/* Hadamard rotation: the fast Walsh-Hadamard transform of a matrix along one axis,
+ * in consecutive segments of L = m 2^k elements.  H = M (x) H_{2^k}: H_{2^k} Sylvester's matrix, M the
+ * m x m matrix `mix` (fp32 on the device, row-major; NULL when m = 1), a Hadamard matrix of order m.
+ * pre: an optional fp32 device vector, one factor per index along the transformed axis (NULL: ones).
+ *
+ *   awq_hadamard_rows: in, out [R, K], L | K.  For every row and every L-segment of it
+ *       out_seg = ((in_seg * pre_seg) H) / sqrt(L)                          (pre: [K])
+ *   awq_hadamard_cols: in, out [K, N], L | K, N % 8 == 0.  For every column and every L-segment of rows
+ *       out_seg = H^T (pre_seg * in_seg) / sqrt(L)                          (pre: [K], one per row)
+ *
+ * Both compute out[j' P + p'] = sum_{j, p} M[j][j'] H_P[p][p'] (pre x)[j P + p] / sqrt(L), P = 2^k:
+ * log2 P stages of additions and subtractions, m fused multiply-adds per element where m > 1, one
+ * multiplication by pre and one by 1 / sqrt(L), one rounding (to nearest even) into the dtype.
+ * fp32 matrices: fp32 arithmetic, per segment ||out - exact||_2 <= (log2 L + m + 4) 2^-24 ||exact||_2.
+ * 16-bit matrices: fp64 arithmetic, so that an output that cancels to nearly zero (whose 16-bit ulp is
+ * far below the fp32 error of its sum) is still the rounding of the exact value.
+ * dtype: AWQ_DTYPE_BF16 / F16 / F32, of in and out alike.  Supported: m in {1, 12, 20, 28}, 2^k >= 16,
+ * L <= 16384; anything else is AWQ_EINVAL / AWQ_EUNSUPPORTED with nothing launched.  An empty matrix
+ * returns AWQ_OK and looks at no pointer.  in, out, work: 16-B aligned (rows: pre too).
+ * awq_hadamard_cols takes one pass per factor of L (csrc/awq_hadamard.hip): one for L <= 128, two or
+ * three beyond; between passes the values of a 16-bit matrix stay fp64 in `work`, awq_hadamard_cols_work_bytes(...)
+ * = 8 K N bytes of device memory (0 for one pass and for fp32 matrices, which use `out`; then work may be NULL).
+ * Launches go to the caller's stream; no allocation, no synchronisation, no global state. */
+int awq_hadamard_rows(const void* in, int dtype, int64_t R, int64_t K, int64_t L, int m, const float* pre,
+                      const float* mix, void* out, void* stream);
+int awq_hadamard_cols(const void* in, int dtype, int64_t K, int64_t N, int64_t L, int m, const float* pre,
+                      const float* mix, void* out, void* work, void* stream);
+int64_t awq_hadamard_cols_work_bytes(int dtype, int64_t K, int64_t N, int64_t L, int m);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
