@@ -163,6 +163,10 @@ SIGNATURES = {
     "awq_hadamard_rows": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _P]),
     "awq_hadamard_cols": (_I32, [_P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _P, _P]),
     "awq_hadamard_cols_work_bytes": (_I64, [_I32, _I64, _I64, _I64, _I32]),
+    "awq_quantize_mxfp4": (_I32, [_P, _I32, _I64, _I64, _I32, _P, _P, _P]),
+    "awq_dequantize_mxfp4": (_I32, [_P, _P, _I64, _I64, _I32, _P, _P]),
+    "awq_mxfp4_error_out_bytes": (_I64, [_I64, _I64]),
+    "awq_mxfp4_error": (_I32, [_P, _I32, _P, _P, _I64, _I64, _P, _P]),
 }
 
 _lib = None
@@ -990,3 +994,49 @@ def hadamard_cols(x: torch.Tensor, L: int, m: int, pre, mix, out: torch.Tensor) 
     work = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device) if nbytes else None
     check(lib.awq_hadamard_cols(ptr(x), AWQ_DTYPE[x.dtype], K, N, L, m, ptr(pre), ptr(mix), ptr(out), ptr(work),
                                 _stream(x)), "awq_hadamard_cols")
+
+
+# ---- MXFP4 weights (include/awq_hip.h awq_quantize_mxfp4 / awq_dequantize_mxfp4 / awq_mxfp4_error) ----
+MXFP4_RULES = {"floor": 0, "ceil": 1, "mse": 2}
+
+
+def _mxfp4_pair(codes: torch.Tensor, scales: torch.Tensor, rows: int, K: int) -> None:
+    for t, shape, what in ((codes, (rows, K // 2), "codes"), (scales, (rows, K // 32), "scales")):
+        if t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"mxfp4 {what} must be a contiguous uint8 device tensor {shape}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+
+
+def quantize_mxfp4(x: torch.Tensor, rule: str, codes: torch.Tensor, scales: torch.Tensor) -> None:
+    """awq_quantize_mxfp4: x [rows, K] (bf16 / fp16 / fp32, device, contiguous) -> codes uint8 [rows, K / 2],
+    scales uint8 [rows, K / 32] under the scale rule "floor", "ceil" or "mse"."""
+    if rule not in MXFP4_RULES:
+        raise ValueError(f"mxfp4 scale rule must be one of {sorted(MXFP4_RULES)}, got {rule!r}")
+    rows, K = x.shape
+    if K % 32 == 0:
+        _mxfp4_pair(codes, scales, rows, K)
+    check(load_library().awq_quantize_mxfp4(ptr(x), AWQ_DTYPE.get(x.dtype, -1), rows, K, MXFP4_RULES[rule], ptr(codes),
+                                            ptr(scales), _stream(x)), "awq_quantize_mxfp4")
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor, out: torch.Tensor) -> None:
+    """awq_dequantize_mxfp4: out [rows, K] (bf16 / fp16 / fp32) = +-mag 2^(e - 127), rounded once."""
+    rows, K = out.shape
+    _mxfp4_pair(codes, scales, rows, K)
+    check(load_library().awq_dequantize_mxfp4(ptr(codes), ptr(scales), rows, K, AWQ_DTYPE.get(out.dtype, -1), ptr(out),
+                                              _stream(out)), "awq_dequantize_mxfp4")
+
+
+def mxfp4_error(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """awq_mxfp4_error: fp64 [5] on x's device — sum |d|, sum d^2, sum w^2, max |d| and the non-finite
+    count of d = x - dequantize(codes, scales).  Allocates the entry's output and workspace."""
+    rows, K = x.shape
+    _mxfp4_pair(codes, scales, rows, K)
+    lib = load_library()
+    nbytes = lib.awq_mxfp4_error_out_bytes(rows, K)
+    if nbytes < 0:
+        raise RuntimeError(f"awq_mxfp4_error: a [{rows}, {K}] tensor is beyond the report's range")
+    out = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    check(lib.awq_mxfp4_error(ptr(x), AWQ_DTYPE.get(x.dtype, -1), ptr(codes), ptr(scales), rows, K, ptr(out),
+                              _stream(x)), "awq_mxfp4_error")
+    return out[:5]

@@ -10,7 +10,10 @@ runs the quantized model exactly as it runs the source.
       used as it stands: folded norms, biases and rows with scaled-domain weights;
   gptq (the same files + quantize_config.json with quant_method "gptq"): the same, every linear
       imported through awq_import_gptq when its g_idx is k // group_size, and dequantized in one
-      pass by awq_dequantize_gptq when it is not (act-order, desc_act true).
+      pass by awq_dequantize_gptq when it is not (act-order, desc_act true; DESIGN.md §5.20);
+  mxfp4 (the same files, config.json's quantization_config saying quant_method "mxfp4"): every
+      `<prefix>.weight` with a `.weight_scale` beside it is dequantized to fp32 by awq_dequantize_mxfp4
+      (exact: DESIGN.md §5.22), every other tensor is read as written.
 
 Tensors the directory does not hold come from the source.  `dequant` does the arithmetic:
 DeviceDequant runs the library's kernels (awq_dequantize, awq_dequantize_packed,
@@ -25,8 +28,8 @@ from typing import Dict, List
 
 import torch
 
-from ..verify import (CHUNK_STEM, _split_flat, autoawq_files, is_autoawq_dir, is_gptq_dir, read_gptq_config,
-                      read_quant_config)
+from ..verify import (CHUNK_STEM, _split_flat, autoawq_files, is_autoawq_dir, is_gptq_dir, is_mxfp4_dir,
+                      read_gptq_config, read_quant_config)
 
 _GEMM_KEYS = ("qweight", "qzeros", "scales")
 
@@ -58,6 +61,10 @@ class DeviceDequant:
         return self.q.dequantize_gptq(gptq, group_size=group_size, symmetric=symmetric,
                                       checkpoint_format=checkpoint_format)
 
+    def mxfp4(self, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+        from ..quantization.mxfp4 import stored_result
+        return self.q.dequantize_mxfp4(stored_result(codes, scales), torch.float32)
+
     def unscale(self, w: torch.Tensor, input_scale: torch.Tensor) -> torch.Tensor:
         return w.float() / input_scale.to(w.device, torch.float32)[None, :]
 
@@ -74,13 +81,16 @@ class QuantizedCheckpoint:
         self._lock = threading.Lock()         # run_decoder reads the next block ahead on a worker thread
         if is_autoawq_dir(quantized_dir):
             from safetensors import safe_open
-            self.format = "gptq" if is_gptq_dir(quantized_dir) else "autoawq"
-            read = read_gptq_config if self.format == "gptq" else read_quant_config
-            cfg, problems = read(quantized_dir)
-            if problems:
-                raise ValueError("; ".join(f"{k}: {v}" for k, v in problems.items()))
-            self._gs, self._sym = cfg["group_size"], cfg["symmetric"]
-            self._ckpt_format = cfg.get("checkpoint_format")
+            if is_mxfp4_dir(quantized_dir):
+                self.format = "mxfp4"
+            else:
+                self.format = "gptq" if is_gptq_dir(quantized_dir) else "autoawq"
+                read = read_gptq_config if self.format == "gptq" else read_quant_config
+                cfg, problems = read(quantized_dir)
+                if problems:
+                    raise ValueError("; ".join(f"{k}: {v}" for k, v in problems.items()))
+                self._gs, self._sym = cfg["group_size"], cfg["symmetric"]
+                self._ckpt_format = cfg.get("checkpoint_format")
             self._where: Dict[str, object] = {}
             for shard in autoawq_files(quantized_dir):
                 h = safe_open(shard, framework="pt")
@@ -104,6 +114,8 @@ class QuantizedCheckpoint:
         """The tensors that are dequantized from the directory (source names)."""
         if self.format == "chunks":
             return list(self._chunk_of)
+        if self.format == "mxfp4":
+            return sorted(n for n in self._where if n.endswith(".weight") and f"{n}_scale" in self._where)
         return sorted(n[: -len("qweight")] + "weight" for n in self._where
                       if n.endswith(".qweight") and all(n[: -len("qweight")] + k in self._where for k in _GEMM_KEYS))
 
@@ -137,6 +149,9 @@ class QuantizedCheckpoint:
             if "input_scale" in res:
                 w = self.dequant.unscale(w, res["input_scale"])
             return w
+        if self.format == "mxfp4" and name.endswith(".weight") and f"{name}_scale" in self._where:
+            return self.dequant.mxfp4(self._where[name].get_tensor(name),
+                                      self._where[f"{name}_scale"].get_tensor(f"{name}_scale"))
         layer = name[: -len(".weight")] if name.endswith(".weight") else None
         if layer is not None and all(f"{layer}.{k}" in self._where for k in _GEMM_KEYS):
             gemm = {k: self._where[f"{layer}.{k}"].get_tensor(f"{layer}.{k}") for k in _GEMM_KEYS}

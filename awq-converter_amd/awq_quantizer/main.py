@@ -340,6 +340,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         elif args.scale_method == "awq":
             logger.warning("--scale_method awq without --act_stats: every weight is quantized RTN")
 
+        if args.output_format == "mxfp4":   # tensor by tensor in one process
+            from .mxfp4_cli import main_mxfp4
+            return main_mxfp4(args, loader, index, ordered, devices[0], logger, start)
+
         cfg = StreamSettings.from_args(args, packed=args.output_format in ("packed",) + CHECKPOINT_FORMATS,
                                        export_autoawq=autoawq,
                                        export_gptq=args.gptq_format if args.output_format == "gptq" else None, act_stats=act_stats, act_clip=act_clip_of(args))

@@ -91,13 +91,20 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--save_safetensors", action="store_true", help="Save in safetensors format instead of pytorch format")
     p.add_argument("--chunk_size", type=int, default=10, help="Number of tensors to save in each chunk (for large models)")
     # extension (not in the reference)
-    p.add_argument("--output_format", type=str, default="reference", choices=["reference", "packed", "autoawq", "gptq"],
+    p.add_argument("--output_format", type=str, default="reference",
+                   choices=["reference", "packed", "autoawq", "gptq", "mxfp4"],
                    help="reference: int32 tensor_q/zero_points + fp16 scales per tensor (reference layout); "
                         "packed: int32 qweight/qzeros (bits-packed) + fp16 scales; "
                         "autoawq: a 4-bit checkpoint in AutoAWQ's GEMM layout (linear weights quantized, "
                         "everything else copied) + quant_config.json; "
                         "gptq: the same in AutoGPTQ's 4-bit layout (desc_act false; --symmetric is honoured) + "
-                        "quantize_config.json")
+                        "quantize_config.json; "
+                        "mxfp4: OCP microscaling FP4 (blocks of 32, E8M0 scales, E2M1 elements): <prefix>.weight "
+                        "uint8 [N, K/2] + <prefix>.weight_scale uint8 [N, K/32] per linear, everything else copied")
+    p.add_argument("--mxfp4_scale", type=str, default=None, choices=["floor", "ceil", "mse"],
+                   help="--output_format mxfp4: the block scale's rule. floor (the default): the OCP MX "
+                        "specification's; ceil: one step up where an element would saturate; mse: whichever of "
+                        "the two has the smaller squared error, per block")
     p.add_argument("--gptq_format", type=str, default="gptq", choices=["gptq", "gptq_v2"],
                    help="--output_format gptq: the checkpoint_format. gptq (v1, what transformers and vLLM read) "
                         "stores zero point - 1 modulo 16; gptq_v2 stores the zero point itself")
@@ -138,6 +145,35 @@ GPTQ_ONE_PROCESS = "--output_format gptq runs in one process (it is not written 
 CHECKPOINT_FORMATS = ("autoawq", "gptq")
 
 
+MXFP4_ONE_PROCESS = "--output_format mxfp4 runs in one process (it is not written under torchrun)"
+MXFP4_SCALE_METHOD = ("--output_format mxfp4 takes --scale_method minmax or mse (round to nearest): a block's scale is "
+                      "a power of two chosen by --mxfp4_scale, not a searched one")
+MXFP4_NO_FOLD = "--output_format mxfp4 refuses --fold_scales: activation-aware MXFP4 is not implemented"
+MXFP4_NO_CLIP = "--output_format mxfp4 refuses --act_clip: a power-of-two scale has no range to clip"
+MXFP4_NO_GPTQ = "--output_format mxfp4 refuses --rounding gptq: error-compensated MXFP4 is not implemented"
+MXFP4_BITS = "--output_format mxfp4 writes 4-bit elements (E2M1): --bits 8 does not apply"
+MXFP4_SCALE_NEEDS = "--mxfp4_scale is read by --output_format mxfp4"
+
+
+def check_mxfp4(args, world: int = 1) -> Optional[str]:
+    """What --output_format mxfp4 refuses, one message each (world: torchrun's WORLD_SIZE)."""
+    if args.output_format != "mxfp4":
+        return MXFP4_SCALE_NEEDS if getattr(args, "mxfp4_scale", None) else None
+    if world > 1:
+        return MXFP4_ONE_PROCESS
+    if args.scale_method in ("search", "awq"):
+        return MXFP4_SCALE_METHOD
+    if args.fold_scales:
+        return MXFP4_NO_FOLD
+    if args.act_clip:
+        return MXFP4_NO_CLIP
+    if getattr(args, "rounding", "nearest") == "gptq":
+        return MXFP4_NO_GPTQ
+    if args.bits != 4:
+        return MXFP4_BITS
+    return None
+
+
 ACT_ORDER_NEEDS = ("--gptq_act_order needs --rounding gptq and --output_format gptq (act-order is the solver's column "
                    "order, and only the GPTQ layout has a g_idx to record it)")
 
@@ -145,6 +181,9 @@ ACT_ORDER_NEEDS = ("--gptq_act_order needs --rounding gptq and --output_format g
 def check_flags(args) -> Optional[str]:
     """The rules that need nothing but the flags: main() applies them before it touches a
     device or the model.  The first error's message, or None."""
+    err = check_mxfp4(args)
+    if err:
+        return err
     if getattr(args, "gptq_act_order", False) and (getattr(args, "rounding", "nearest") != "gptq"
                                                    or args.output_format != "gptq"):
         return ACT_ORDER_NEEDS
@@ -201,7 +240,7 @@ def check_args(args, world: int, n_devices: int, model_type: Optional[str]) -> O
     message, or None for a run that may start.  world: torchrun's WORLD_SIZE (1 without it);
     n_devices: GPUs this process drives; model_type: config.json's, if any (only --fold_scales
     asks)."""
-    err = check_flags(args)
+    err = check_mxfp4(args, world) or check_flags(args)
     if err:
         return err
     stats = has_stats(args)

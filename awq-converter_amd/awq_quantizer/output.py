@@ -398,6 +398,48 @@ def save_autoawq(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthro
                     f"{len(passthrough) + len(failed)} tensors copied")
 
 
+MXFP4_QUANT_METHOD = "mxfp4"
+
+
+def write_mxfp4_config(output_dir: str, loader, scale_rule: str, not_converted: List[str]) -> None:
+    """config.json: the source's (when it has one) plus a `quantization_config` naming the format, its
+    block size, the scale rule and the linear modules left unconverted.  Always written: it is what
+    marks the directory as MXFP4 for verify and evaluate."""
+    cfg = {}
+    src = os.path.join(getattr(loader, "model_path", "") or "", "config.json")
+    if os.path.isfile(src):
+        with open(src) as f:
+            cfg = json.load(f)
+    cfg["quantization_config"] = {"quant_method": MXFP4_QUANT_METHOD, "weight_format": "mxfp4", "block_size": 32,
+                                  "scale_format": "e8m0", "element_format": "e2m1", "scale_rule": scale_rule,
+                                  "modules_to_not_convert": list(not_converted)}
+    with open(os.path.join(output_dir, "config.json"), "w") as f:
+        json.dump(cfg, f, indent=2)
+
+
+def save_mxfp4(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthrough: List[TensorInfo],
+               output_dir: str, scale_rule: str, logger=None, failed: List[TensorInfo] = ()) -> None:
+    """model.safetensors with `<prefix>.weight` (the codes) and `<prefix>.weight_scale` (the scale bytes)
+    for every converted linear and every other tensor copied unchanged (linear weights that failed
+    included, listed in modules_to_not_convert), plus write_mxfp4_config's config.json."""
+    from safetensors.torch import save_file
+    tensors = {}
+    for name, r in quantized.items():
+        tensors[name] = r["codes"].contiguous()
+        tensors[f"{name}_scale"] = r["scales"].contiguous()
+    for info in list(passthrough) + list(failed):
+        tensors[info.name] = loader.read(info).contiguous()
+    save_file(tensors, os.path.join(output_dir, "model.safetensors"), metadata={"format": "pt"})
+    not_converted = [i.name[: -len(".weight")] for i in failed]
+    write_mxfp4_config(output_dir, loader, scale_rule, not_converted)
+    if logger:
+        if not_converted:
+            logger.warning(f"{len(not_converted)} linear weight(s) failed to quantize and were copied unquantized "
+                           f"(modules_to_not_convert): {not_converted}")
+        logger.info(f"Saved MXFP4 checkpoint: {len(quantized)} quantized linear weights, "
+                    f"{len(passthrough) + len(failed)} tensors copied")
+
+
 def cpu_share() -> int:
     """CPUs this process may actually use: its affinity set, capped by a cgroup v2 CPU quota
     (`cpu.max`) — os.cpu_count() reports the whole machine, which on a shared GPU node is

@@ -26,7 +26,7 @@ This module is the class: its state, its checks, the reference API and quantize_
 other method is a delegate to a function that takes the quantizer first — reference_private.py
 (the reference's private methods), batch.py (whole models), act_search.py (activation-aware),
 autoawq.py (AutoAWQ in and out), gptq.py (GPTQ in and out), gptq_round.py (GPTQ's error-compensated
-rounding), report.py (the error report) — imported when first called; shapes and result metadata
+rounding), mxfp4.py (MXFP4 weights), report.py (the error report) — imported when first called; shapes and result metadata
 come from ../layout.py.
 """
 
@@ -622,7 +622,10 @@ class AWQQuantizer:
         the ORIGINAL domain — the original tensor, w^ = dq / input_scale, unscaled samples: the
         layer as the model runs it after the fold — while the weight-space figures above stay in
         the scaled domain.  A shape mismatch raises ValueError before any device work."""
-        from .report import quantization_error
+        if result.get("format") == "mxfp4":
+            from .mxfp4 import quantization_error
+        else:
+            from .report import quantization_error
         return quantization_error(self, tensor, result, per_group, samples)
 
     def quantization_error_model(self, tensors: Dict[str, torch.Tensor],
@@ -631,6 +634,25 @@ class AWQQuantizer:
         are logged and skipped, like quantize_model."""
         from .report import quantization_error_model
         return quantization_error_model(self, tensors, results)
+
+    # ------------------------------------------------------------------ MXFP4 weights
+    def quantize_mxfp4(self, tensor: torch.Tensor, scale_rule: str = "floor") -> Dict[str, torch.Tensor]:
+        """A 2-D weight [N, K], K % 32 == 0, bf16 / fp16 / fp32, as OCP microscaling FP4 (include/awq_hip.h
+        awq_quantize_mxfp4): {"codes": uint8 [N, K / 2] (E2M1, the even element in a
+        byte's low nibble), "scales": uint8 [N, K / 32] (E8M0, one per 32 elements of a row), "format":
+        "mxfp4", "shape", "scale_rule"}, codes and scales left on the compute device as quantize_packed
+        leaves its outputs.  scale_rule: "floor" (the OCP specification's), "ceil" (no element saturates)
+        or "mse" (whichever of the two has the smaller squared error, per block).  The format fixes the
+        block and the element type: the quantizer's bits, group_size and symmetric are not consulted."""
+        from .mxfp4 import quantize_mxfp4
+        return quantize_mxfp4(self, tensor, scale_rule)
+
+    def dequantize_mxfp4(self, result: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """The weight a quantize_mxfp4 result stands for: [N, K] of dtype (bf16 / fp16 / fp32) on the
+        compute device, every value rounded once (awq_dequantize_mxfp4); a block whose scale byte is 255
+        is NaN.  The quantizer's bits, group_size and symmetric are not consulted."""
+        from .mxfp4 import dequantize_mxfp4
+        return dequantize_mxfp4(self, result, dtype)
 
     def hadamard_transform(self, x: torch.Tensor, dim: int, *, length: Optional[int] = None,
                            pre: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -214,6 +214,8 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
         from .quantization.awq import AWQQuantizer
         quantizer = AWQQuantizer(device=args.device, logger_name="awq_verify_quantizer", logger_level="WARNING")
         error_fn = quantizer.quantization_error
+    if is_mxfp4_dir(args.quantized_dir):
+        return verify_mxfp4(args, loader, index, error_fn, logger)
     if is_autoawq_dir(args.quantized_dir):
         made = []
 
@@ -624,6 +626,105 @@ def verify_autoawq(args: argparse.Namespace, loader, index: Dict[str, object], e
     log_worst(entries, args.worst, logger)
     report = write_report(path, entries, problems, echo, skipped,
                           extra={"layout": layout, "copied": copied, "fold_audited": has_sidecar})
+    t = report["totals"]
+    logger.info(f"{t['tensors']} tensors, {t['numel']} elements: mean_abs_error {t['mean_abs_error']:.6g}  "
+                f"snr {t['snr_db']:.2f} dB  nonfinite {t['nonfinite']}; {len(copied)} copied; report: {path}")
+    return 1 if problems else 0
+
+
+# ---------------------------------------------------------------- MXFP4 directories
+def read_mxfp4_config(quantized_dir: str) -> Optional[dict]:
+    """config.json's quantization_config of an --output_format mxfp4 directory; None for any other."""
+    try:
+        with open(os.path.join(quantized_dir, "config.json")) as f:
+            cfg = json.load(f).get("quantization_config")
+    except (OSError, ValueError, AttributeError):
+        return None
+    return cfg if isinstance(cfg, dict) and cfg.get("quant_method") == "mxfp4" else None
+
+
+def is_mxfp4_dir(quantized_dir: str) -> bool:
+    return is_autoawq_dir(quantized_dir) and read_mxfp4_config(quantized_dir) is not None
+
+
+def verify_mxfp4(args: argparse.Namespace, loader, index: Dict[str, object], error_fn: Callable, logger) -> int:
+    """verify() for an --output_format mxfp4 directory: every `<prefix>.weight` with a `.weight_scale`
+    beside it is reported through error_fn (awq_mxfp4_error) against the source; every other tensor
+    must be the source's bytes.  Findings (exit code 1): a converted tensor without a source, of another
+    shape or listed as unconverted, a block marked NaN (scale byte 255) whose source block is finite, a
+    copied tensor that differs, a source tensor that is missing."""
+    from safetensors import safe_open
+    from .quantization.mxfp4 import stored_result
+    d = args.quantized_dir
+    cfg = read_mxfp4_config(d)
+    entries: Dict[str, dict] = {}
+    problems: Dict[str, str] = {}
+    copied: List[str] = []
+
+    def problem(name: str, why: str) -> None:
+        problems[name] = why
+        logger.error(f"{name}: {why}")
+
+    handles = []
+    try:
+        where: Dict[str, object] = {}
+        for shard in autoawq_files(d):
+            h = safe_open(shard, framework="pt")
+            handles.append(h)
+            for k in h.keys():
+                where[k] = h
+        converted = sorted(n for n in where if n.endswith(".weight") and f"{n}_scale" in where)
+        for name in converted:
+            info = index.get(name)
+            codes, scales = where[name].get_tensor(name), where[f"{name}_scale"].get_tensor(f"{name}_scale")
+            if info is None:
+                problem(name, "no source tensor of this name")
+                continue
+            if name[: -len(".weight")] in cfg.get("modules_to_not_convert", []):
+                problem(name, "quantized although config.json lists it in modules_to_not_convert")
+                continue
+            shape = (int(codes.shape[0]), int(codes.shape[-1]) * 2) if codes.dim() == 2 else tuple(codes.shape)
+            if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or tuple(info.shape) != shape \
+                    or tuple(scales.shape) != (shape[0], shape[1] // 32):
+                problem(name, f"codes {codes.dtype} {list(codes.shape)} / scales {scales.dtype} {list(scales.shape)} "
+                              f"do not fit source shape {list(info.shape)}")
+                continue
+            try:
+                w = loader.read(info)
+                e = error_fn(w, stored_result(codes, scales))
+            except Exception as ex:  # noqa: BLE001
+                problem(name, f"{type(ex).__name__}: {ex}")
+                continue
+            entries[name] = {k: e[k] for k in _ENTRY_KEYS}
+            entries[name].update(input_scaled=False, layout="mxfp4")
+            logger.info(f"{name}: mean_abs_error {e['mean_abs_error']:.6g}  max {e['max_abs_error']:.6g}  "
+                        f"snr {e['snr_db']:.2f} dB  nonfinite {e['nonfinite']}")
+            marked = w.reshape(shape[0], shape[1] // 32, 32)[scales == 255]      # the source of the blocks marked NaN
+            stray = int(torch.isfinite(marked.float()).all(-1).sum())
+            if stray:
+                problem(name, f"{stray} block(s) marked NaN (scale byte 255) whose source block is finite")
+        in_pair = set(converted) | {f"{n}_scale" for n in converted}
+        for name in sorted(n for n in where if n not in in_pair):
+            info = index.get(name)
+            if info is None:
+                problem(name, "copied tensor with no source tensor of this name")
+                continue
+            copied.append(name)
+            if not same_bytes(where[name].get_tensor(name), loader.read(info)):
+                problem(name, "copied tensor differs from the source's bytes")
+        for name in index:
+            if name not in where:
+                problem(name, "source tensor missing from the checkpoint")
+    except Exception as e:  # noqa: BLE001
+        logger.error(f"Failed to read the quantized checkpoint {d}: {e}")
+        return 1
+    finally:
+        loader.close()
+        del handles
+    log_worst(entries, args.worst, logger)
+    path = args.report or os.path.join(d, "quantization_error.json")
+    report = write_report(path, entries, problems, {"model_id": args.model_id, "quantized_dir": d},
+                          extra={"layout": "mxfp4", "copied": copied, "scale_rule": cfg.get("scale_rule")})
     t = report["totals"]
     logger.info(f"{t['tensors']} tensors, {t['numel']} elements: mean_abs_error {t['mean_abs_error']:.6g}  "
                 f"snr {t['snr_db']:.2f} dB  nonfinite {t['nonfinite']}; {len(copied)} copied; report: {path}")

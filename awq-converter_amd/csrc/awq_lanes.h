@@ -206,6 +206,32 @@ __device__ __forceinline__ T wave_max_up(T v) {
     return v;
 }
 
+// ---- the error report's per-chunk statistics (awq_qerror.hip, awq_mxfp4.hip) ----
+// One chunk's elements accumulated in element order from +0 (include/awq_hip.h awq_quant_error):
+// d = RN_f32(w - dq), a = |d|, e = RN_f32(d d), p = RN_f32(w w); an element whose e or p is NaN / inf
+// adds nothing to the sums or the max and counts 1.  The group's figures are grp_sum / grp_max of these.
+struct ErrAcc {
+    float a = 0.0f, e = 0.0f, p = 0.0f, m = 0.0f;
+    int bad = 0;
+    __device__ __forceinline__ void add_dq(float w, float dq) {
+        const float d = w - dq;
+        const float ab = __builtin_fabsf(d), sq = d * d, ww = w * w;
+        const bool fin = sq < __builtin_inff() && ww < __builtin_inff();   // NaN compares false
+        a = a + (fin ? ab : 0.0f);
+        e = e + (fin ? sq : 0.0f);
+        p = p + (fin ? ww : 0.0f);
+        m = __builtin_fmaxf(m, fin ? ab : 0.0f);
+        bad += fin ? 0 : 1;
+    }
+};
+
 }  // namespace
+
+// the report's level 2 (awq_qerror.hip): the fp64 totals [5] of per-group figures, in awq_quant_error's
+// order.  qerror_level2_blocks: its 1024-group blocks (-1: beyond the reduce's range); work holds 5
+// doubles per block.
+int64_t qerror_level2_blocks(int64_t n_groups);
+hipError_t launch_qerror_totals(const float* group_stats, const int32_t* group_nonfinite, int64_t n_groups,
+                                double* work, double* totals, hipStream_t stream);
 }  // namespace awq
 #endif  // AWQ_LANES_H

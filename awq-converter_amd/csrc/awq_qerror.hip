@@ -25,21 +25,12 @@ constexpr int kMaxGroup = 512;             // 64 chunk slots of 8 elements
 constexpr int kGroupBlock2 = 1024;         // groups per level-2 block (= awq_act_search_select's)
 constexpr int64_t kMaxBlocks2 = 6144 * 32; // blocks awq_act_search_select's last level takes
 
-// The statistics of one chunk's elements, accumulated in element order.
-struct Acc {
-    float a = 0.0f, e = 0.0f, p = 0.0f, m = 0.0f;
-    int bad = 0;
+// The statistics of one chunk's elements, accumulated in element order: ErrAcc (awq_lanes.h, shared
+// with awq_mxfp4_error) fed with this file's dequantized value.
+struct Acc : ErrAcc {
     // w: the weight as fp32; diff = q - z; s: the fp16 scale's value
     __device__ __forceinline__ void add(float w, int diff, float s) {
-        const float dq = (float)(_Float16)((float)diff * s);   // exact product, one RNE to fp16
-        const float d = w - dq;
-        const float ab = __builtin_fabsf(d), sq = d * d, ww = w * w;
-        const bool fin = sq < __builtin_inff() && ww < __builtin_inff();   // NaN compares false
-        a = a + (fin ? ab : 0.0f);
-        e = e + (fin ? sq : 0.0f);
-        p = p + (fin ? ww : 0.0f);
-        m = __builtin_fmaxf(m, fin ? ab : 0.0f);
-        bad += fin ? 0 : 1;
+        add_dq(w, (float)(_Float16)((float)diff * s));   // exact product, one RNE to fp16
     }
 };
 
@@ -333,6 +324,20 @@ void launch_stream(int gs, unsigned tiles, hipStream_t st, const void* w, const 
 }
 
 }  // namespace
+
+// level 2 of the report (declared in awq_lanes.h; awq_mxfp4_error's too): the per-tensor fp64 totals of
+// group_stats fp32 [4, ng] / group_nonfinite int32 [ng]; work: 5 doubles per 1024-group block
+int64_t qerror_level2_blocks(int64_t n_groups) { return n_groups > kMaxBlocks2 * kGroupBlock2 ? -1 : level2_blocks(n_groups); }
+hipError_t launch_qerror_totals(const float* group_stats, const int32_t* group_nonfinite, int64_t ng, double* work,
+                                double* totals, hipStream_t st) {
+    const int64_t nblk = level2_blocks(ng);
+    hipError_t e = launch_act_select(group_stats, 3, ng, nullptr, 0, work, totals, nullptr, nullptr, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(qerror_block_kernel, dim3((unsigned)nblk), dim3(256), 0, st, group_stats + 3 * ng,
+                       group_nonfinite, ng, work + 3 * nblk, work + 4 * nblk);
+    hipLaunchKernelGGL(qerror_final_kernel, dim3(1), dim3(256), 0, st, work + 3 * nblk, work + 4 * nblk, nblk, totals);
+    return hipPeekAtLastError();
+}
 }  // namespace awq
 
 using namespace awq;
@@ -395,16 +400,6 @@ extern "C" int awq_quant_error(const void* w, int dtype, int64_t rows, int64_t K
 #undef AWQ_QE_GEN
     }
     e = hipPeekAtLastError();
-    if (e == hipSuccess && totals) {
-        const int64_t nblk = level2_blocks(ng);
-        e = launch_act_select(group_stats, 3, ng, nullptr, 0, work, totals, nullptr, nullptr, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(qerror_block_kernel, dim3((unsigned)nblk), dim3(256), 0, st, group_stats + 3 * ng,
-                               group_nonfinite, ng, work + 3 * nblk, work + 4 * nblk);
-            hipLaunchKernelGGL(qerror_final_kernel, dim3(1), dim3(256), 0, st, work + 3 * nblk, work + 4 * nblk, nblk,
-                               totals);
-            e = hipPeekAtLastError();
-        }
-    }
+    if (e == hipSuccess && totals) e = launch_qerror_totals(group_stats, group_nonfinite, ng, work, totals, st);
     return hip_status(e, "awq quant error kernels");
 }

@@ -1022,6 +1022,41 @@ int awq_hadamard_cols(const void* in, int dtype, int64_t K, int64_t N, int64_t L
                       const float* mix, void* out, void* work, void* stream);
 int64_t awq_hadamard_cols_work_bytes(int dtype, int64_t K, int64_t N, int64_t L, int m);
 
+/* MXFP4 weights (additive, the ABI number stays): OCP microscaling FP4.  A weight
+ * [rows, K], K % 32 == 0, bf16 / fp16 / fp32, in blocks of 32 consecutive elements of a row:
+ *   scales uint8 [rows, K / 32]: E8M0, the byte e stands for 2^(e - 127), e = 255 for NaN;
+ *   codes  uint8 [rows, K / 2]:  E2M1, bit 3 the sign, bits 2..0 an index into 0, 0.5, 1, 1.5, 2, 3, 4, 6;
+ *                                element 2j in the low nibble of byte j, 2j + 1 in the high one.
+ * Scale rules, amax = max |x| over the block, X = e - 127:
+ *   AWQ_MXFP4_FLOOR  X = clamp(floor(log2 amax) - 2, -127, 127) (the OCP MX specification); amax == 0: X = 0;
+ *   AWQ_MXFP4_CEIL   the floor rule's X, plus one iff amax 2^-X > 6: no element saturates;
+ *   AWQ_MXFP4_MSE    the floor rule's X, plus one iff sum (x - dq(x))^2 over the block is strictly smaller
+ *                    with X + 1 (fp32 sums of the errors scaled by 2^-X: a lane's 8 elements in order from
+ *                    +0, then the tree over the block's 4 lanes, adjacent pairs first).
+ * Elements: |x| 2^-X (exact) to the nearest magnitude, a tie to the even index, above 6 to 6; the sign
+ * bit is x's (a zero keeps it).  A block holding a NaN or an inf: e = 255, all codes 0.
+ * Dequantize: +-mag 2^(e - 127) rounded once, to nearest even, into out_dtype (bf16 / fp16 / fp32;
+ * beyond the type's range inf); e = 255: the block is NaN.
+ * awq_mxfp4_error: awq_quant_error's figures of d = w - dequantize(codes, scales) with this format's
+ * exact fp32 value as dq, level 1 per block of 32 (one 8-element chunk per lane, the tree over 4 lanes),
+ * level 2 as there; an element of a block with e = 255 counts as non-finite.  out: device memory of
+ * awq_mxfp4_error_out_bytes(rows, K) bytes (< 0: rows K / 32 beyond the level-2 reduce's range), 8-B
+ * aligned; its first five doubles are the totals (sum |d|, sum d^2, sum w^2, max |d|, non-finite count),
+ * the rest is workspace.
+ * Checked in this order, nothing launched on a failure: a negative rows or K, K % 32 != 0, a dtype that is
+ * not bf16 / fp16 / fp32 (AWQ_EINVAL); rows K > 2^60 (AWQ_EUNSUPPORTED); the rule (AWQ_EINVAL); rows K == 0: AWQ_OK,
+ * no pointer is looked at (awq_mxfp4_error zeroes the totals); a NULL pointer; x or a dequantized out not
+ * 16-B aligned, codes not 4-B, quantize's scales not 4-B (AWQ_EINVAL).  Any size below 2^60 elements:
+ * every index is 64-bit.  Launches go to the caller's stream; no allocation, no synchronisation. */
+enum { AWQ_MXFP4_FLOOR = 0, AWQ_MXFP4_CEIL = 1, AWQ_MXFP4_MSE = 2 };
+int awq_quantize_mxfp4(const void* x, int dtype, int64_t rows, int64_t K, int rule, uint8_t* codes,
+                       uint8_t* scales, void* stream);
+int awq_dequantize_mxfp4(const uint8_t* codes, const uint8_t* scales, int64_t rows, int64_t K, int out_dtype,
+                         void* out, void* stream);
+int64_t awq_mxfp4_error_out_bytes(int64_t rows, int64_t K);
+int awq_mxfp4_error(const void* x, int dtype, const uint8_t* codes, const uint8_t* scales, int64_t rows,
+                    int64_t K, void* out, void* stream);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
