@@ -167,6 +167,7 @@ SIGNATURES = {
     "awq_dequantize_mxfp4": (_I32, [_P, _P, _I64, _I64, _I32, _P, _P]),
     "awq_mxfp4_error_out_bytes": (_I64, [_I64, _I64]),
     "awq_mxfp4_error": (_I32, [_P, _I32, _P, _P, _I64, _I64, _P, _P]),
+    "awq_gptq_round_block_mxfp4": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _I64, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -1040,3 +1041,23 @@ def mxfp4_error(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> t
     check(lib.awq_mxfp4_error(ptr(x), AWQ_DTYPE.get(x.dtype, -1), ptr(codes), ptr(scales), rows, K, ptr(out),
                               _stream(x)), "awq_mxfp4_error")
     return out[:5]
+
+
+def gptq_round_block_mxfp4(work: torch.Tensor, u: torch.Tensor, rule: str, col_begin: int, n_cols: int,
+                           err: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> None:
+    """awq_gptq_round_block_mxfp4: GPTQ's in-block loop on the E2M1 grid over columns [col_begin, col_begin +
+    n_cols) of the fp32 working weights work [N, K] (device, contiguous, updated in place) with the fp32
+    [K, K] upper factor u of the inverse Hessian; err fp32 [N, n_cols] receives the scaled errors, and the
+    call's code bytes and scale bytes of the MXFP4 result are written."""
+    if rule not in MXFP4_RULES:
+        raise ValueError(f"mxfp4 scale rule must be one of {sorted(MXFP4_RULES)}, got {rule!r}")
+    N, K = work.shape
+    for t, dt, shape, what in ((work, torch.float32, (N, K), "work"), (u, torch.float32, (K, K), "u"),
+                               (err, torch.float32, (N, n_cols), "err")):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != work.device:
+            raise ValueError(f"awq_gptq_round_block_mxfp4: {what} must be a contiguous {dt} {shape} on {work.device}")
+    if K % 32 == 0:
+        _mxfp4_pair(codes, scales, N, K)
+    check(load_library().awq_gptq_round_block_mxfp4(ptr(work), N, K, MXFP4_RULES[rule], ptr(u), col_begin, n_cols,
+                                                    ptr(err), ptr(codes), ptr(scales), _stream(work)),
+          "awq_gptq_round_block_mxfp4")

@@ -105,6 +105,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--output_format mxfp4: the block scale's rule. floor (the default): the OCP MX "
                         "specification's; ceil: one step up where an element would saturate; mse: whichever of "
                         "the two has the smaller squared error, per block")
+    p.add_argument("--mxfp4_rounding", type=str, default=None, choices=["nearest", "gptq"],
+                   help="--output_format mxfp4: how the E2M1 codes are chosen. nearest (the default): round to "
+                        "nearest; gptq: GPTQ's error-compensated rounding on the E2M1 grid, solved per layer group on "
+                        "the token samples of --act_samples (--gptq_damp and --gptq_factor apply); a linear without "
+                        "samples rounds to nearest")
     p.add_argument("--gptq_format", type=str, default="gptq", choices=["gptq", "gptq_v2"],
                    help="--output_format gptq: the checkpoint_format. gptq (v1, what transformers and vLLM read) "
                         "stores zero point - 1 modulo 16; gptq_v2 stores the zero point itself")
@@ -125,7 +130,13 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
 
 def wants_samples(args) -> bool:
     """A search of this run scores its candidates on token samples, or --rounding gptq solves on them."""
-    return args.search_loss == "output" or args.clip_loss == "output" or getattr(args, "rounding", "nearest") == "gptq"
+    return (args.search_loss == "output" or args.clip_loss == "output" or getattr(args, "rounding", "nearest") == "gptq"
+            or mxfp4_gptq(args))
+
+
+def mxfp4_gptq(args) -> bool:
+    """--output_format mxfp4 --mxfp4_rounding gptq: the solver on the E2M1 grid."""
+    return args.output_format == "mxfp4" and getattr(args, "mxfp4_rounding", None) == "gptq"
 
 
 def has_stats(args) -> bool:
@@ -153,12 +164,17 @@ MXFP4_NO_CLIP = "--output_format mxfp4 refuses --act_clip: a power-of-two scale 
 MXFP4_NO_GPTQ = "--output_format mxfp4 refuses --rounding gptq: error-compensated MXFP4 is not implemented"
 MXFP4_BITS = "--output_format mxfp4 writes 4-bit elements (E2M1): --bits 8 does not apply"
 MXFP4_SCALE_NEEDS = "--mxfp4_scale is read by --output_format mxfp4"
+MXFP4_ROUNDING_NEEDS = "--mxfp4_rounding is read by --output_format mxfp4"
+MXFP4_GPTQ_SAMPLES = ("--mxfp4_rounding gptq needs token samples: --act_samples FILE (awq_quantizer.calibrate "
+                      "--samples_output)")
 
 
 def check_mxfp4(args, world: int = 1) -> Optional[str]:
     """What --output_format mxfp4 refuses, one message each (world: torchrun's WORLD_SIZE)."""
     if args.output_format != "mxfp4":
-        return MXFP4_SCALE_NEEDS if getattr(args, "mxfp4_scale", None) else None
+        if getattr(args, "mxfp4_scale", None):
+            return MXFP4_SCALE_NEEDS
+        return MXFP4_ROUNDING_NEEDS if getattr(args, "mxfp4_rounding", None) else None
     if world > 1:
         return MXFP4_ONE_PROCESS
     if args.scale_method in ("search", "awq"):
@@ -171,6 +187,11 @@ def check_mxfp4(args, world: int = 1) -> Optional[str]:
         return MXFP4_NO_GPTQ
     if args.bits != 4:
         return MXFP4_BITS
+    if mxfp4_gptq(args):
+        if not args.act_samples:
+            return MXFP4_GPTQ_SAMPLES
+        if not 0.0 < getattr(args, "gptq_damp", 0.01) < 1.0:
+            return "--gptq_damp must be in (0, 1)"
     return None
 
 
@@ -230,7 +251,7 @@ def check_flags(args) -> Optional[str]:
             return "--rounding gptq refuses --act_clip: the solver moves the ranges the clip search chose"
         if not 0.0 < getattr(args, "gptq_damp", 0.01) < 1.0:
             return "--gptq_damp must be in (0, 1)"
-    elif getattr(args, "gptq_factor", "torch") != "torch":
+    elif getattr(args, "gptq_factor", "torch") != "torch" and not mxfp4_gptq(args):
         return "--gptq_factor is read by --rounding gptq"
     return None
 

@@ -401,10 +401,12 @@ def save_autoawq(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthro
 MXFP4_QUANT_METHOD = "mxfp4"
 
 
-def write_mxfp4_config(output_dir: str, loader, scale_rule: str, not_converted: List[str]) -> None:
+def write_mxfp4_config(output_dir: str, loader, scale_rule: str, not_converted: List[str],
+                       rounding: Optional[dict] = None) -> None:
     """config.json: the source's (when it has one) plus a `quantization_config` naming the format, its
-    block size, the scale rule and the linear modules left unconverted.  Always written: it is what
-    marks the directory as MXFP4 for verify and evaluate."""
+    block size, the scale rule and the linear modules left unconverted; rounding ({"rounding": "gptq",
+    "damp": ...} from --mxfp4_rounding gptq) adds how the codes were chosen.  Always
+    written: it is what marks the directory as MXFP4 for verify and evaluate."""
     cfg = {}
     src = os.path.join(getattr(loader, "model_path", "") or "", "config.json")
     if os.path.isfile(src):
@@ -413,12 +415,14 @@ def write_mxfp4_config(output_dir: str, loader, scale_rule: str, not_converted: 
     cfg["quantization_config"] = {"quant_method": MXFP4_QUANT_METHOD, "weight_format": "mxfp4", "block_size": 32,
                                   "scale_format": "e8m0", "element_format": "e2m1", "scale_rule": scale_rule,
                                   "modules_to_not_convert": list(not_converted)}
+    cfg["quantization_config"].update(rounding or {})
     with open(os.path.join(output_dir, "config.json"), "w") as f:
         json.dump(cfg, f, indent=2)
 
 
 def save_mxfp4(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthrough: List[TensorInfo],
-               output_dir: str, scale_rule: str, logger=None, failed: List[TensorInfo] = ()) -> None:
+               output_dir: str, scale_rule: str, logger=None, failed: List[TensorInfo] = (),
+               rounding: Optional[dict] = None) -> None:
     """model.safetensors with `<prefix>.weight` (the codes) and `<prefix>.weight_scale` (the scale bytes)
     for every converted linear and every other tensor copied unchanged (linear weights that failed
     included, listed in modules_to_not_convert), plus write_mxfp4_config's config.json."""
@@ -431,7 +435,7 @@ def save_mxfp4(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthroug
         tensors[info.name] = loader.read(info).contiguous()
     save_file(tensors, os.path.join(output_dir, "model.safetensors"), metadata={"format": "pt"})
     not_converted = [i.name[: -len(".weight")] for i in failed]
-    write_mxfp4_config(output_dir, loader, scale_rule, not_converted)
+    write_mxfp4_config(output_dir, loader, scale_rule, not_converted, rounding)
     if logger:
         if not_converted:
             logger.warning(f"{len(not_converted)} linear weight(s) failed to quantize and were copied unquantized "

@@ -647,6 +647,18 @@ class AWQQuantizer:
         from .mxfp4 import quantize_mxfp4
         return quantize_mxfp4(self, tensor, scale_rule)
 
+    def quantize_gptq_mxfp4(self, tensor: torch.Tensor, samples: Optional[torch.Tensor] = None, *,
+                            hessian: Optional[torch.Tensor] = None, scale_rule: str = "floor",
+                            damp: float = 0.01) -> Dict[str, torch.Tensor]:
+        """quantize_mxfp4 with GPTQ's error-compensated rounding on the E2M1 grid instead of
+        round-to-nearest (gptq_mxfp4.py; include/awq_hip.h awq_gptq_round_block_mxfp4):
+        a quantize_mxfp4 result with the same keys, plus "rounding": {"loss", "loss_rtn",
+        "dead_columns", "damp", "fallback", "factor"} as quantize_gptq reports them.  samples
+        [tokens, K] or hessian [K, K]; self.gptq_factor is honoured.  No act_order and no input_scale
+        (gptq_mxfp4.py's docstring says why)."""
+        from .gptq_mxfp4 import quantize_gptq_mxfp4
+        return quantize_gptq_mxfp4(self, tensor, samples, hessian=hessian, scale_rule=scale_rule, damp=damp)
+
     def dequantize_mxfp4(self, result: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """The weight a quantize_mxfp4 result stands for: [N, K] of dtype (bf16 / fp16 / fp32) on the
         compute device, every value rounded once (awq_dequantize_mxfp4); a block whose scale byte is 255

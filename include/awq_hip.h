@@ -1057,6 +1057,31 @@ int64_t awq_mxfp4_error_out_bytes(int64_t rows, int64_t K);
 int awq_mxfp4_error(const void* x, int dtype, const uint8_t* codes, const uint8_t* scales, int64_t rows,
                     int64_t K, void* out, void* stream);
 
+/* GPTQ error-compensated rounding onto the MXFP4 grid (additive, the ABI number stays):
+ * awq_gptq_round_block's chain with awq_quantize_mxfp4's scale rule and element rounding.  work fp32 [N, K]
+ * (updated in place over the call's columns), u fp32 [K, K] the upper factor with H^-1 = U^T U, the call's
+ * columns [col_begin, col_begin + n_cols); one row, column c = col_begin + i, every operation one fp32
+ * operation rounded on its own:
+ *   at a block's first column (c % 32 == 0), from the block's 32 working values as they stand now: if any
+ *   is NaN or inf, scale byte 255, all 32 codes 0, err = 0 for the block's columns, nothing propagated from
+ *   them, the working values left as they are; otherwise the scale exponent X (byte X + 127) is
+ *   awq_quantize_mxfp4's for fp32 input under `rule`, the "mse" sums in the scaled domain of X in fp32, four
+ *   runs of 8 elements in order from +0 combined as (p0 + p1) + (p2 + p3), up iff 4 s1 < s0;
+ *   column c: t = |w| 2^-X, v = min(t, 6), the one fp32 addition of 2^(22 + max(exponent of v, 0)) gives
+ *   the magnitude index and the rounded magnitude m; dq = +-m 2^X (exact; the sign and the code's sign bit
+ *   are w's); d = w - dq; e = d / U[c][c] (IEEE division), 0 where w, dq or the quotient is not finite;
+ *   err[row][i] = e; every later column j of the call becomes w_j - RN(e U[c][j]).
+ * codes uint8 [N, K / 2] (the low nibble the even element) and scales uint8 [N, K / 32]: only the call's
+ * columns and blocks are written; err fp32 [N, n_cols].  The caller updates the columns right of the call
+ * (work[:, col_begin + n_cols:] -= err U[call rows, those columns]).
+ * Checked in this order, nothing launched on a failure: a negative size; the rule; K % 32 != 0; n_cols not a
+ * multiple of 32 or above 128; col_begin not a multiple of 32 or col_begin + n_cols > K (AWQ_EINVAL); N, K or
+ * n_cols == 0: AWQ_OK, no pointer is looked at; N or K above 2^31 - 1 (AWQ_EUNSUPPORTED); a NULL pointer;
+ * work, u or err not 16-B aligned, codes not 4-B (AWQ_EINVAL).  The launch goes to the caller's stream; no
+ * allocation, no synchronisation, no global state. */
+int awq_gptq_round_block_mxfp4(float* work, int64_t N, int64_t K, int rule, const float* u, int64_t col_begin,
+                               int64_t n_cols, float* err, uint8_t* codes, uint8_t* scales, void* stream);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
