@@ -168,6 +168,8 @@ SIGNATURES = {
     "awq_mxfp4_error_out_bytes": (_I64, [_I64, _I64]),
     "awq_mxfp4_error": (_I32, [_P, _I32, _P, _P, _I64, _I64, _P, _P]),
     "awq_gptq_round_block_mxfp4": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _I64, _P, _P, _P, _P]),
+    "awq_act_search_losses_mxfp4": (_I32, [_P, _I32, _I64, _I64, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
+    "awq_quantize_mxfp4_scaled": (_I32, [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -1061,3 +1063,43 @@ def gptq_round_block_mxfp4(work: torch.Tensor, u: torch.Tensor, rule: str, col_b
     check(load_library().awq_gptq_round_block_mxfp4(ptr(work), N, K, MXFP4_RULES[rule], ptr(u), col_begin, n_cols,
                                                     ptr(err), ptr(codes), ptr(scales), _stream(work)),
           "awq_gptq_round_block_mxfp4")
+
+
+def act_search_losses_mxfp4(weights, x_sq: torch.Tensor, table: torch.Tensor, rule: str,
+                            rtable: Optional[torch.Tensor] = None, use_rtable: bool = True) -> torch.Tensor:
+    """awq_act_search_losses_mxfp4 per weight into one buffer: part fp32 [n_grid, total blocks of all
+    weights], each weight's blocks at its offset.  rtable: act_recip_table(table) (computed here unless
+    given; use_rtable=False: IEEE divisions, the same bits)."""
+    if rule not in MXFP4_RULES:
+        raise ValueError(f"mxfp4 scale rule must be one of {sorted(MXFP4_RULES)}, got {rule!r}")
+    lib = load_library()
+    n_grid, K = table.shape
+    if use_rtable and rtable is None:
+        rtable = act_recip_table(table)
+    if not use_rtable:
+        rtable = None
+    blocks = [w.shape[0] * (K // 32) for w in weights]
+    stride = sum(blocks)
+    part = torch.empty((n_grid, stride), dtype=torch.float32, device=table.device)
+    off = 0
+    for w, b in zip(weights, blocks):
+        check(lib.awq_act_search_losses_mxfp4(ptr(w), AWQ_DTYPE.get(w.dtype, -1), w.shape[0], K, MXFP4_RULES[rule],
+                                              ptr(table), ptr(rtable), n_grid, ptr(x_sq),
+                                              ctypes.c_void_p(part.data_ptr() + 4 * off), stride, _stream(w)),
+              "awq_act_search_losses_mxfp4")
+        off += b
+    return part
+
+
+def quantize_mxfp4_scaled(w: torch.Tensor, s: torch.Tensor, rule: str, codes: torch.Tensor,
+                          scales: torch.Tensor) -> None:
+    """awq_quantize_mxfp4_scaled: the MXFP4 codes and scales of w * diag(s) (w [rows, K] device, contiguous;
+    s fp32 [K]) in one pass, the bytes of quantize_mxfp4(apply_input_scale(w, s))."""
+    if rule not in MXFP4_RULES:
+        raise ValueError(f"mxfp4 scale rule must be one of {sorted(MXFP4_RULES)}, got {rule!r}")
+    rows, K = w.shape
+    if K % 32 == 0:
+        _mxfp4_pair(codes, scales, rows, K)
+    check(load_library().awq_quantize_mxfp4_scaled(ptr(w), AWQ_DTYPE.get(w.dtype, -1), rows, K, MXFP4_RULES[rule],
+                                                   ptr(s), ptr(codes), ptr(scales), _stream(w)),
+          "awq_quantize_mxfp4_scaled")

@@ -342,7 +342,8 @@ def main(argv: Optional[List[str]] = None) -> int:
 
         if args.output_format == "mxfp4":   # tensor by tensor in one process
             from .mxfp4_cli import main_mxfp4
-            return main_mxfp4(args, loader, index, ordered, devices[0], logger, start, act_samples=act_samples)
+            return main_mxfp4(args, loader, index, ordered, devices[0], logger, start, act_samples=act_samples,
+                              act_stats=act_stats if args.mxfp4_act_scales else None)
 
         cfg = StreamSettings.from_args(args, packed=args.output_format in ("packed",) + CHECKPOINT_FORMATS,
                                        export_autoawq=autoawq,

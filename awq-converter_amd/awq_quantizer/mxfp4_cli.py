@@ -8,7 +8,13 @@ format).  The directory: model.safetensors with `<prefix>.weight` (uint8 [N, K /
 --mxfp4_rounding gptq: a linear whose layer group (block_plan.plan_blocks) has token
 samples `<block prefix>.<group>.samples` in --act_samples goes through quantize_gptq_mxfp4; the Hessian
 and its factor are built once per group and every member is solved against them.  A linear without
-samples (lm_head, ungrouped, a model type block_plan does not know) rounds to nearest."""
+samples (lm_head, ungrouped, a model type block_plan does not know) rounds to nearest.
+
+--mxfp4_act_scales --act_stats FILE: the decoder blocks of plan_blocks(..., 32) one by one
+through AWQQuantizer.quantize_block_mxfp4; the folded norm weights and biases are written in place of the
+source's, awq_scales.safetensors holds every block's scales (the keys --fold_scales writes) and the
+quantization_config records "input_scales": "awq".  A linear in no block, or of a block that failed, is
+quantized as without the flag."""
 import time
 from typing import Dict, List, Optional
 
@@ -29,7 +35,7 @@ def sample_keys(index: List[TensorInfo], linear: List[TensorInfo], mtype: Option
 
 
 def main_mxfp4(args, loader, index: List[TensorInfo], ordered: List[TensorInfo], device: str, logger,
-               start: float, act_samples: Optional[dict] = None) -> int:
+               start: float, act_samples: Optional[dict] = None, act_stats: Optional[dict] = None) -> int:
     import torch
 
     from .quantization.awq import AWQQuantizer
@@ -50,7 +56,32 @@ def main_mxfp4(args, loader, index: List[TensorInfo], ordered: List[TensorInfo],
         q.gptq_factor = args.gptq_factor
         keys = sample_keys(index, linear, mtype)
     quantized, failed = {}, []
+    overrides, sidecar = {}, {}
+    if act_stats is not None:
+        from .quantization.block_plan import plan_blocks
+        by_name = {i.name: i for i in index}
+        plan = plan_blocks({i.name: tuple(i.shape) for i in index}, mtype, BLOCK)
+        blocks = [b for b in plan if all(m in names for m in b.members())]
+        logger.info(f"--mxfp4_act_scales: {len(blocks)} decoder blocks, {sum(len(b.members()) for b in blocks)} linears "
+                    f"in layer groups")
+        for block in blocks:
+            try:
+                out = q.quantize_block_mxfp4({n: loader.read(by_name[n]) for n in block.tensor_names()}, act_stats,
+                                             block, scale_rule=rule)
+                done = {n: {"codes": r["codes"].cpu(), "scales": r["scales"].cpu()} for n, r in out["results"].items()}
+                host_folded = {n: t.cpu() for n, t in out["folded"].items()}
+                host_scales = {n: t.cpu() for n, t in out["scales"].items()}
+            except Exception as e:  # noqa: BLE001  (the block's linears take the plain path below, nothing folded)
+                logger.error(f"Error quantizing block {block.prefix}: {e}")
+                continue
+            quantized.update(done)
+            overrides.update(host_folded)
+            sidecar.update(host_scales)
+            logger.info(f"Successfully quantized block: {block.prefix} (folded groups: "
+                        f"{[n for n, g in out['groups'].items() if g['folded']]})")
     for info in linear:
+        if info.name in quantized:
+            continue
         try:
             w = loader.read(info)
             xs = (act_samples or {}).get(keys.get(info.name))
@@ -75,5 +106,16 @@ def main_mxfp4(args, loader, index: List[TensorInfo], ordered: List[TensorInfo],
                     f"({n_fallback} fell back), {n_nearest} without samples rounded to nearest")
     TIMINGS["quantize_s"] = time.time() - start
     rounding = {"rounding": "gptq", "damp": args.gptq_damp} if gptq else {"rounding": "nearest"}
-    return finish_run(args, linear, quantized, logger, start,
-                      lambda: save_mxfp4(quantized, loader, passthrough, args.output_dir, rule, logger, failed, rounding))
+    if act_stats is not None:
+        rounding["input_scales"] = "awq"
+    quantized = {i.name: quantized[i.name] for i in linear if i.name in quantized}      # the source's order
+
+    def save():
+        save_mxfp4(quantized, loader, passthrough, args.output_dir, rule, logger, failed, rounding, overrides)
+        if act_stats is not None:
+            import os
+
+            from safetensors.torch import save_file
+            save_file({k: v.contiguous() for k, v in sidecar.items()},
+                      os.path.join(args.output_dir, "awq_scales.safetensors"), metadata={"format": "pt"})
+    return finish_run(args, linear, quantized, logger, start, save)

@@ -110,6 +110,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "nearest; gptq: GPTQ's error-compensated rounding on the E2M1 grid, solved per layer group on "
                         "the token samples of --act_samples (--gptq_damp and --gptq_factor apply); a linear without "
                         "samples rounds to nearest")
+    p.add_argument("--mxfp4_act_scales", action="store_true",
+                   help="--output_format mxfp4 with --act_stats FILE: search one input scale per layer group with "
+                        "every candidate scored on the MXFP4 grid, fold 1/s into the op producing the input and "
+                        "write awq_scales.safetensors (DESIGN.md 5.24); not with --mxfp4_rounding gptq")
     p.add_argument("--gptq_format", type=str, default="gptq", choices=["gptq", "gptq_v2"],
                    help="--output_format gptq: the checkpoint_format. gptq (v1, what transformers and vLLM read) "
                         "stores zero point - 1 modulo 16; gptq_v2 stores the zero point itself")
@@ -159,12 +163,16 @@ CHECKPOINT_FORMATS = ("autoawq", "gptq")
 MXFP4_ONE_PROCESS = "--output_format mxfp4 runs in one process (it is not written under torchrun)"
 MXFP4_SCALE_METHOD = ("--output_format mxfp4 takes --scale_method minmax or mse (round to nearest): a block's scale is "
                       "a power of two chosen by --mxfp4_scale, not a searched one")
-MXFP4_NO_FOLD = "--output_format mxfp4 refuses --fold_scales: activation-aware MXFP4 is not implemented"
+MXFP4_NO_FOLD = "--output_format mxfp4 refuses --fold_scales: its searched scales are --mxfp4_act_scales"
 MXFP4_NO_CLIP = "--output_format mxfp4 refuses --act_clip: a power-of-two scale has no range to clip"
 MXFP4_NO_GPTQ = "--output_format mxfp4 refuses --rounding gptq: error-compensated MXFP4 is not implemented"
 MXFP4_BITS = "--output_format mxfp4 writes 4-bit elements (E2M1): --bits 8 does not apply"
 MXFP4_SCALE_NEEDS = "--mxfp4_scale is read by --output_format mxfp4"
 MXFP4_ROUNDING_NEEDS = "--mxfp4_rounding is read by --output_format mxfp4"
+MXFP4_ACT_NEEDS = "--mxfp4_act_scales is read by --output_format mxfp4"
+MXFP4_ACT_STATS = "--mxfp4_act_scales needs activation statistics: --act_stats FILE (awq_quantizer.calibrate)"
+MXFP4_ACT_NO_GPTQ = ("--mxfp4_act_scales refuses --mxfp4_rounding gptq: GPTQ rounding on top of the searched scales is "
+                     "not composed")
 MXFP4_GPTQ_SAMPLES = ("--mxfp4_rounding gptq needs token samples: --act_samples FILE (awq_quantizer.calibrate "
                       "--samples_output)")
 
@@ -172,6 +180,8 @@ MXFP4_GPTQ_SAMPLES = ("--mxfp4_rounding gptq needs token samples: --act_samples 
 def check_mxfp4(args, world: int = 1) -> Optional[str]:
     """What --output_format mxfp4 refuses, one message each (world: torchrun's WORLD_SIZE)."""
     if args.output_format != "mxfp4":
+        if getattr(args, "mxfp4_act_scales", False):
+            return MXFP4_ACT_NEEDS
         if getattr(args, "mxfp4_scale", None):
             return MXFP4_SCALE_NEEDS
         return MXFP4_ROUNDING_NEEDS if getattr(args, "mxfp4_rounding", None) else None
@@ -187,6 +197,11 @@ def check_mxfp4(args, world: int = 1) -> Optional[str]:
         return MXFP4_NO_GPTQ
     if args.bits != 4:
         return MXFP4_BITS
+    if getattr(args, "mxfp4_act_scales", False):
+        if mxfp4_gptq(args):
+            return MXFP4_ACT_NO_GPTQ
+        if not args.act_stats:
+            return MXFP4_ACT_STATS
     if mxfp4_gptq(args):
         if not args.act_samples:
             return MXFP4_GPTQ_SAMPLES
@@ -291,7 +306,7 @@ def check_args(args, world: int, n_devices: int, model_type: Optional[str]) -> O
         if args.clip_grid < 1 or not 0.0 <= args.clip_max_shrink <= 1.0:
             return "--act_clip needs --clip_grid >= 1 and --clip_max_shrink in [0, 1]"
     if stats:
-        if args.scale_method != "awq":
+        if args.scale_method != "awq" and not getattr(args, "mxfp4_act_scales", False):
             return f"{'--calib_ids' if args.calib_ids else '--act_stats'} needs --scale_method awq"
         if gptq and not args.fold_scales:
             return ("--act_stats with --output_format gptq: the searched input scales must be folded "

@@ -422,17 +422,19 @@ def write_mxfp4_config(output_dir: str, loader, scale_rule: str, not_converted: 
 
 def save_mxfp4(quantized: Dict[str, Dict[str, torch.Tensor]], loader, passthrough: List[TensorInfo],
                output_dir: str, scale_rule: str, logger=None, failed: List[TensorInfo] = (),
-               rounding: Optional[dict] = None) -> None:
+               rounding: Optional[dict] = None, overrides: Optional[Dict[str, torch.Tensor]] = None) -> None:
     """model.safetensors with `<prefix>.weight` (the codes) and `<prefix>.weight_scale` (the scale bytes)
     for every converted linear and every other tensor copied unchanged (linear weights that failed
-    included, listed in modules_to_not_convert), plus write_mxfp4_config's config.json."""
+    included, listed in modules_to_not_convert) or, where `overrides` names it (--mxfp4_act_scales' folded
+    norm weights and biases), replaced, plus write_mxfp4_config's config.json."""
     from safetensors.torch import save_file
     tensors = {}
     for name, r in quantized.items():
         tensors[name] = r["codes"].contiguous()
         tensors[f"{name}_scale"] = r["scales"].contiguous()
     for info in list(passthrough) + list(failed):
-        tensors[info.name] = loader.read(info).contiguous()
+        t = (overrides or {}).get(info.name)
+        tensors[info.name] = (loader.read(info) if t is None else t).contiguous()
     save_file(tensors, os.path.join(output_dir, "model.safetensors"), metadata={"format": "pt"})
     not_converted = [i.name[: -len(".weight")] for i in failed]
     write_mxfp4_config(output_dir, loader, scale_rule, not_converted, rounding)

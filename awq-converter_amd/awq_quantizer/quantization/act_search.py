@@ -49,17 +49,12 @@ def _check_group(weights: Dict[str, torch.Tensor], group_size: int):
     return K
 
 
-def search_layer_group(weights: Dict[str, torch.Tensor], device: torch.device, *, group_size: int, bits: int,
-                       symmetric: bool, n_grid: int, duo_scaling: bool,
-                       activations: Optional[torch.Tensor] = None, x_mean: Optional[torch.Tensor] = None,
-                       x_sq: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None,
-                       scale_weights: bool = True) -> dict:
-    """Run the search on the device; returns device tensors
-    {"x_mean", "x_sq", "w_mean", "table", "losses", "best", "input_scale", "weights": {name: W on
-    the device}, "scaled": {name: W·diag(s)} (None with scale_weights=False: the caller
-    quantizes W·diag(s) in one pass, awq_quantize_groups_scaled)}.
-    `table` overrides the scale table (a caller's own table; since round 5 the kernel's table
-    is bit-exact with the oracle's from the inputs alone, include/awq_hip.h awq_pow)."""
+def group_inputs(weights: Dict[str, torch.Tensor], device: torch.device, *, group_size: int, n_grid: int,
+                 duo_scaling: bool, activations: Optional[torch.Tensor] = None,
+                 x_mean: Optional[torch.Tensor] = None, x_sq: Optional[torch.Tensor] = None,
+                 table: Optional[torch.Tensor] = None):
+    """What every search of a layer group starts from, on the device: (the weights, x_mean, x_sq, w_mean
+    at `group_size` (None without duo scaling), the scale table [n_grid, K])."""
     K = _check_group(weights, group_size)
     if not 1 <= n_grid <= _hip.ACT_MAX_GRID:
         raise ValueError(f"search_grid must be in [1, {_hip.ACT_MAX_GRID}] for scale_method='awq': {n_grid}")
@@ -83,6 +78,23 @@ def search_layer_group(weights: Dict[str, torch.Tensor], device: torch.device, *
         table = table.detach().to(device, torch.float32).contiguous()
         if tuple(table.shape) != (n_grid, K):
             raise ValueError(f"table must be [{n_grid}, {K}]")
+    return ws, x_mean, x_sq, w_mean, table
+
+
+def search_layer_group(weights: Dict[str, torch.Tensor], device: torch.device, *, group_size: int, bits: int,
+                       symmetric: bool, n_grid: int, duo_scaling: bool,
+                       activations: Optional[torch.Tensor] = None, x_mean: Optional[torch.Tensor] = None,
+                       x_sq: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None,
+                       scale_weights: bool = True) -> dict:
+    """Run the search on the device; returns device tensors
+    {"x_mean", "x_sq", "w_mean", "table", "losses", "best", "input_scale", "weights": {name: W on
+    the device}, "scaled": {name: W·diag(s)} (None with scale_weights=False: the caller
+    quantizes W·diag(s) in one pass, awq_quantize_groups_scaled)}.
+    `table` overrides the scale table (a caller's own table; since round 5 the kernel's table
+    is bit-exact with the oracle's from the inputs alone, include/awq_hip.h awq_pow)."""
+    ws, x_mean, x_sq, w_mean, table = group_inputs(weights, device, group_size=group_size, n_grid=n_grid,
+                                                   duo_scaling=duo_scaling, activations=activations,
+                                                   x_mean=x_mean, x_sq=x_sq, table=table)
     part = _hip.act_search_losses(ws, x_sq, table, group_size, bits, symmetric)
     losses, best, s_best = _hip.act_search_select(part, table)
     scaled = {name: _hip.apply_input_scale(w, s_best) for name, w in zip(weights, ws)} if scale_weights else None
@@ -300,6 +312,20 @@ def clip_layer_group(q, weights, sr: dict, clip_grid: int, n_clip: int,
             "losses": sr["losses"], "table": sr["table"], "clip": clip}
 
 
+def group_stats(q, stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]], g):
+    """The statistics of a layer group: its first member's that has any (None: none has), with a warning
+    for every other member whose statistics differ (they read the same input)."""
+    have = [m for m in g.members if m in stats]
+    if not have:
+        return None
+    first = stats[have[0]]
+    for m in have[1:]:
+        if not (torch.equal(stats[m][0], first[0]) and torch.equal(stats[m][1], first[1])):
+            q.logger.warning(f"{m}: activation statistics differ from {have[0]}'s (same input): "
+                             f"using {have[0]}'s for the {g.name} group")
+    return first
+
+
 def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
                    block, *, clip: bool = False, clip_grid: int = 20, clip_max_shrink: float = 0.5,
                    samples: Optional[Dict[str, torch.Tensor]] = None, loss: str = "diag",
@@ -322,20 +348,9 @@ def quantize_block(q, tensors: Dict[str, torch.Tensor], stats: Dict[str, Tuple[t
             current[name] = tensors[name].detach().to(dev).contiguous()
         return current[name]
 
-    def group_stats(g):
-        have = [m for m in g.members if m in stats]
-        if not have:
-            return None
-        first = stats[have[0]]
-        for m in have[1:]:
-            if not (torch.equal(stats[m][0], first[0]) and torch.equal(stats[m][1], first[1])):
-                q.logger.warning(f"{m}: activation statistics differ from {have[0]}'s (same input): "
-                                    f"using {have[0]}'s for the {g.name} group")
-        return first
-
     def run(g) -> Optional[torch.Tensor]:
         weights = {m: dev_t(m) for m in g.members}
-        st = group_stats(g)
+        st = group_stats(q, stats, g)
         K = next(iter(weights.values())).shape[1]
         fold = g.foldable and st is not None
         if fold or (clip and st is not None):

@@ -647,6 +647,25 @@ class AWQQuantizer:
         from .mxfp4 import quantize_mxfp4
         return quantize_mxfp4(self, tensor, scale_rule)
 
+    def quantize_layer_group_mxfp4(self, weights: Dict[str, torch.Tensor], activations: Optional[torch.Tensor] = None,
+                                   *, x_mean: Optional[torch.Tensor] = None, x_sq: Optional[torch.Tensor] = None,
+                                   scale_rule: str = "floor", table: Optional[torch.Tensor] = None) -> dict:
+        """quantize_layer_group's per-input-channel scale search scored on the MXFP4 grid (act_mxfp4.py;
+        include/awq_hip.h awq_act_search_losses_mxfp4), then every weight as MXFP4 of
+        W * diag(input_scale): {"results": {name: a quantize_mxfp4 result + "input_scale"}, "input_scale",
+        "best", "ratio", "losses", "table"}.  search_grid and duo_scaling are the quantizer's."""
+        from .act_mxfp4 import quantize_layer_group_mxfp4
+        return quantize_layer_group_mxfp4(self, weights, activations, x_mean=x_mean, x_sq=x_sq,
+                                          scale_rule=scale_rule, table=table)
+
+    def quantize_block_mxfp4(self, tensors: Dict[str, torch.Tensor],
+                             stats: Dict[str, Tuple[torch.Tensor, torch.Tensor]], block, *,
+                             scale_rule: str = "floor") -> dict:
+        """quantize_block for MXFP4 (act_mxfp4.py): the same order, folds and keys; a group without
+        statistics, or not foldable, is quantized with quantize_mxfp4 and its scale is ones."""
+        from .act_mxfp4 import quantize_block_mxfp4
+        return quantize_block_mxfp4(self, tensors, stats, block, scale_rule=scale_rule)
+
     def quantize_gptq_mxfp4(self, tensor: torch.Tensor, samples: Optional[torch.Tensor] = None, *,
                             hessian: Optional[torch.Tensor] = None, scale_rule: str = "floor",
                             damp: float = 0.01) -> Dict[str, torch.Tensor]:

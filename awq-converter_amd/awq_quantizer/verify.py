@@ -215,7 +215,7 @@ def verify(args: argparse.Namespace, error_fn: Optional[Callable] = None, logger
         quantizer = AWQQuantizer(device=args.device, logger_name="awq_verify_quantizer", logger_level="WARNING")
         error_fn = quantizer.quantization_error
     if is_mxfp4_dir(args.quantized_dir):
-        return verify_mxfp4(args, loader, index, error_fn, logger)
+        return verify_mxfp4(args, loader, index, error_fn, logger, fold_fn)
     if is_autoawq_dir(args.quantized_dir):
         made = []
 
@@ -647,16 +647,34 @@ def is_mxfp4_dir(quantized_dir: str) -> bool:
     return is_autoawq_dir(quantized_dir) and read_mxfp4_config(quantized_dir) is not None
 
 
-def verify_mxfp4(args: argparse.Namespace, loader, index: Dict[str, object], error_fn: Callable, logger) -> int:
+def verify_mxfp4(args: argparse.Namespace, loader, index: Dict[str, object], error_fn: Callable, logger,
+                 fold_fn: Optional[Callable] = None) -> int:
     """verify() for an --output_format mxfp4 directory: every `<prefix>.weight` with a `.weight_scale`
     beside it is reported through error_fn (awq_mxfp4_error) against the source; every other tensor
     must be the source's bytes.  Findings (exit code 1): a converted tensor without a source, of another
     shape or listed as unconverted, a block marked NaN (scale byte 255) whose source block is finite, a
-    copied tensor that differs, a source tensor that is missing."""
+    copied tensor that differs, a source tensor that is missing.
+    With awq_scales.safetensors (--mxfp4_act_scales): every converted linear is measured against the weight
+    in the domain it was quantized in, fold_rows(W, row_scale) * diag(input_scale) rebuilt from the sidecar as
+    verify_autoawq does; the folded norm weights and biases are judged by fold_audit instead of against the
+    source's bytes; a sidecar scale of no converted linear is a finding.  fold_fn(w, s): awq_fold_rows on
+    args.device by default."""
     from safetensors import safe_open
-    from .quantization.mxfp4 import stored_result
+    from .quantization.mxfp4 import BLOCK, stored_result
     d = args.quantized_dir
     cfg = read_mxfp4_config(d)
+    sidecar: Dict[str, torch.Tensor] = {}
+    side_path = os.path.join(d, "awq_scales.safetensors")
+    if os.path.exists(side_path):
+        from safetensors.torch import load_file
+
+        from . import _hip
+        sidecar = load_file(side_path)
+        dev = torch.device(args.device if args.device not in (None, "all") else "cuda")
+
+        def on_dev(t, dtype=None):
+            return t.to(dev, dtype).contiguous()
+        fold_fn = fold_fn or (lambda w, s: _hip.fold_rows(on_dev(w), on_dev(s, torch.float32)))
     entries: Dict[str, dict] = {}
     problems: Dict[str, str] = {}
     copied: List[str] = []
@@ -691,18 +709,36 @@ def verify_mxfp4(args: argparse.Namespace, loader, index: Dict[str, object], err
                 continue
             try:
                 w = loader.read(info)
+                row_scale, in_scale = sidecar.get(f"{name}.row_scale"), sidecar.get(f"{name}.input_scale")
+                if row_scale is not None:
+                    w = fold_fn(w, row_scale)
+                if in_scale is not None:
+                    w = _hip.apply_input_scale(on_dev(w), on_dev(in_scale, torch.float32))
                 e = error_fn(w, stored_result(codes, scales))
+                w = w.cpu()
             except Exception as ex:  # noqa: BLE001
                 problem(name, f"{type(ex).__name__}: {ex}")
                 continue
             entries[name] = {k: e[k] for k in _ENTRY_KEYS}
-            entries[name].update(input_scaled=False, layout="mxfp4")
+            entries[name].update(input_scaled=in_scale is not None, row_folded=row_scale is not None, layout="mxfp4")
             logger.info(f"{name}: mean_abs_error {e['mean_abs_error']:.6g}  max {e['max_abs_error']:.6g}  "
                         f"snr {e['snr_db']:.2f} dB  nonfinite {e['nonfinite']}")
             marked = w.reshape(shape[0], shape[1] // 32, 32)[scales == 255]      # the source of the blocks marked NaN
             stray = int(torch.isfinite(marked.float()).all(-1).sum())
             if stray:
                 problem(name, f"{stray} block(s) marked NaN (scale byte 255) whose source block is finite")
+        judged = set()
+        if sidecar:
+            from .output import model_type_of
+            shapes = {n: tuple(i.shape) for n, i in index.items()}
+            for name, why in fold_audit(shapes, model_type_of(loader), BLOCK, sidecar, lambda n: loader.read(index[n]),
+                                        lambda n: where[n].get_tensor(n) if n in where else None, fold_fn).items():
+                problem(name, why)
+            judged = audited_tensors(shapes, model_type_of(loader), BLOCK)
+            for k in sidecar:
+                lname = k.rpartition(".")[0]
+                if lname not in entries and lname not in problems and k not in problems:
+                    problem(k, "sidecar scale of a tensor that is not a converted linear of the checkpoint")
         in_pair = set(converted) | {f"{n}_scale" for n in converted}
         for name in sorted(n for n in where if n not in in_pair):
             info = index.get(name)
@@ -710,6 +746,8 @@ def verify_mxfp4(args: argparse.Namespace, loader, index: Dict[str, object], err
                 problem(name, "copied tensor with no source tensor of this name")
                 continue
             copied.append(name)
+            if name in judged:
+                continue
             if not same_bytes(where[name].get_tensor(name), loader.read(info)):
                 problem(name, "copied tensor differs from the source's bytes")
         for name in index:
@@ -724,7 +762,8 @@ def verify_mxfp4(args: argparse.Namespace, loader, index: Dict[str, object], err
     log_worst(entries, args.worst, logger)
     path = args.report or os.path.join(d, "quantization_error.json")
     report = write_report(path, entries, problems, {"model_id": args.model_id, "quantized_dir": d},
-                          extra={"layout": "mxfp4", "copied": copied, "scale_rule": cfg.get("scale_rule")})
+                          extra={"layout": "mxfp4", "copied": copied, "scale_rule": cfg.get("scale_rule"),
+                                 "fold_audited": bool(sidecar)})
     t = report["totals"]
     logger.info(f"{t['tensors']} tensors, {t['numel']} elements: mean_abs_error {t['mean_abs_error']:.6g}  "
                 f"snr {t['snr_db']:.2f} dB  nonfinite {t['nonfinite']}; {len(copied)} copied; report: {path}")

@@ -28,57 +28,12 @@
 // (awq_lanes.h: own + lane ^ 1, then + lane ^ 2).
 #include <algorithm>
 
-#include "awq_quant.h"
+#include "awq_mxfp4.h"
 
 namespace awq {
 namespace {
 
-constexpr int kBlockElems = 32;             // elements per MXFP4 block
-constexpr unsigned kQuantWaves = 256 * 32;  // the quantize grid's cap: waves (= one-wave workgroups)
 constexpr unsigned kDequantBlocks = 256 * 16;
-
-// max of the 8 |x| bit patterns of a lane's chunk (sign-magnitude formats: the order of the
-// magnitudes is the order of the patterns)
-template <typename F>
-__device__ __forceinline__ uint32_t lane_absmax(const Chunk<F::NW>& c) {
-    if constexpr (F::NW == 1) {
-        const uint32_t x0 = c.w[0].x & 0x7FFF7FFFu, x1 = c.w[0].y & 0x7FFF7FFFu;
-        const uint32_t x2 = c.w[0].z & 0x7FFF7FFFu, x3 = c.w[0].w & 0x7FFF7FFFu;
-        const us2 m = __builtin_elementwise_max(__builtin_elementwise_max(as_us2(x0), as_us2(x1)),
-                                                __builtin_elementwise_max(as_us2(x2), as_us2(x3)));
-        return max((uint32_t)m.x, (uint32_t)m.y);
-    } else {
-        uint32_t m = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) m = max(m, (uint32_t)c.w[i >> 2][i & 3] & 0x7FFFFFFFu);
-        return m;
-    }
-}
-
-// A lane's 8 elements at the scale 2^-X = inv: the 8 codes as one dword and, with ERR, the sum of
-// (v - rounded v)^2 in element order from +0.
-template <typename F, bool ERR>
-__device__ __forceinline__ uint32_t quant8(const Chunk<F::NW>& c, float inv, float& err) {
-    uint32_t word = 0;
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float x = F::elem(c, i);
-        const float t = __builtin_fabsf(x) * inv;
-        const float v = __builtin_fminf(t, 6.0f);
-        const uint32_t k = max(__float_as_uint(v) >> 23, 127u);        // 127, 128, 129
-        const float magic = __uint_as_float((k + 22u) << 23);
-        const float r = v + magic;                                     // the one rounding
-        const uint32_t code = (__float_as_uint(r) & 7u) + 2u * k - 254u;
-        word |= (code | ((__float_as_uint(x) >> 28) & 8u)) << (4 * i);
-        if (ERR) {
-            const float d = t - (r - magic);
-            s = s + d * d;
-        }
-    }
-    err = s;
-    return word;
-}
 
 // ---------------------------------------------------------------------------------------
 // Quantize.  One wave per trip over a 2048-element segment (awq_internal.h's tile: 4 KiB of 16-bit
@@ -113,43 +68,12 @@ __global__ __launch_bounds__(64) void mxfp4_quant_kernel(const void* __restrict_
         uint32_t eb[4], sd = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t amax = grp_max<4, uint32_t>(lane_absmax<F>(v[j]));
-            const bool bad = amax >= (uint32_t)F::kNanS;                       // exponent all ones
-            const float af = F::dec(amax);
-            uint32_t e = amax == 0u ? 127u : max(__float_as_uint(af) >> 23, 2u) - 2u;
-            const float inv = __uint_as_float((254u - e) << 23);               // 2^-X, e <= 252
-            float s0 = 0.0f, s1 = 0.0f;
             uint32_t word;
-            if (RULE == AWQ_MXFP4_MSE) {
-                word = quant8<F, true>(v[j], inv, s0);
-                const uint32_t w1 = quant8<F, true>(v[j], inv * 0.5f, s1);
-                const bool up = 4.0f * grp_sum<4>(s1) < grp_sum<4>(s0);
-                word = up ? w1 : word;
-                e += up ? 1u : 0u;
-            } else {
-                const bool up = RULE == AWQ_MXFP4_CEIL && af * inv > 6.0f;
-                e += up ? 1u : 0u;
-                word = quant8<F, false>(v[j], up ? inv * 0.5f : inv, s0);
-            }
-            e = bad ? 255u : e;
-            __builtin_amdgcn_raw_buffer_store_b32(bad ? 0u : word, rc, (uint32_t)(j * 256 + lane * 4), 0,
-                                                  AWQ_STORE_AUX);
-            eb[j] = e;
-            uint32_t sb = e << (8 * ((lane >> 2) & 3));
-            sb |= dpp_mov<0x141>(sb);   // row_half_mirror: the row's quads 0 | 1 and 2 | 3
-            sb |= dpp_mov<0x140>(sb);   // row_mirror: all four
-            sd = (lane & 15) == j ? sb : sd;
+            eb[j] = mxfp4_block<F, RULE>(v[j], word);
+            __builtin_amdgcn_raw_buffer_store_b32(word, rc, (uint32_t)(j * 256 + lane * 4), 0, AWQ_STORE_AUX);
+            gather_scale_bytes(eb[j], lane, j, sd);
         }
-        uint8_t* sp = scales + e0 / kBlockElems;
-        if (te == (uint32_t)kTileElems) {
-            if ((lane & 15) < 4) ((uint32_t*)sp)[(lane & 15) * 4 + (lane >> 4)] = sd;
-        } else if ((lane & 3) == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t b = (uint32_t)(j * 16 + (lane >> 2));
-                if (b < te / kBlockElems) sp[b] = (uint8_t)eb[j];
-            }
-        }
+        store_scale_bytes(scales + e0 / kBlockElems, te, lane, sd, eb);
     }
 }
 
@@ -159,9 +83,6 @@ __global__ __launch_bounds__(64) void mxfp4_quant_kernel(const void* __restrict_
 // and 1 are 0 and 0.5.  The product with the scale is exact (two significant bits) down to 2^-128,
 // a subnormal the build keeps, and overflows to inf above fp32's range.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float fp4_scale(uint32_t e) {   // e < 255; e = 0 is the subnormal 2^-127
-    return __uint_as_float(max(e << 23, 0x00400000u));
-}
 __device__ __forceinline__ float fp4_value(uint32_t code, float scale) {
     const uint32_t c = code & 7u;
     const uint32_t mag = c >= 2u ? (c << 22) + 0x3F000000u : c * 0x3F000000u;
@@ -268,18 +189,6 @@ __global__ __launch_bounds__(64) void mxfp4_error_kernel(const void* __restrict_
     }
 }
 
-// what the three entry points check alike: 0 = fine
-int check_common(const char* what, int dtype, int64_t rows, int64_t K) {
-    if (rows < 0 || K < 0) return fail(AWQ_EINVAL, "%s: negative shape (%lld, %lld)", what, (long long)rows, (long long)K);
-    if (K % kBlockElems != 0)
-        return fail(AWQ_EINVAL, "%s: K %% 32 must be 0, the MXFP4 block (K=%lld)", what, (long long)K);
-    if (dtype != AWQ_DTYPE_BF16 && dtype != AWQ_DTYPE_F16 && dtype != AWQ_DTYPE_F32)
-        return fail(AWQ_EINVAL, "%s: dtype code %d is not bf16, fp16 or fp32", what, dtype);
-    if (rows > 0 && K > ((int64_t)1 << 60) / rows)
-        return fail(AWQ_EUNSUPPORTED, "%s: %lld x %lld elements exceed 2^60", what, (long long)rows, (long long)K);
-    return AWQ_OK;
-}
-
 template <typename F>
 void launch_quant(int rule, unsigned grid, hipStream_t st, const void* x, uint8_t* codes, uint8_t* scales, int64_t n,
                   int64_t tiles) {
@@ -314,7 +223,7 @@ using namespace awq;
 extern "C" int awq_quantize_mxfp4(const void* x, int dtype, int64_t rows, int64_t K, int rule, uint8_t* codes,
                                   uint8_t* scales, void* stream) {
     if (int rc = check_common("awq_quantize_mxfp4", dtype, rows, K)) return rc;
-    if (rule != AWQ_MXFP4_FLOOR && rule != AWQ_MXFP4_CEIL && rule != AWQ_MXFP4_MSE)
+    if (!mxfp4_rule_ok(rule))
         return fail(AWQ_EINVAL, "awq_quantize_mxfp4: scale rule %d is not floor (0), ceil (1) or mse (2)", rule);
     const int64_t n = rows * K;
     if (n == 0) return AWQ_OK;

@@ -1082,6 +1082,34 @@ int awq_mxfp4_error(const void* x, int dtype, const uint8_t* codes, const uint8_
 int awq_gptq_round_block_mxfp4(float* work, int64_t N, int64_t K, int rule, const float* u, int64_t col_begin,
                                int64_t n_cols, float* err, uint8_t* codes, uint8_t* scales, void* stream);
 
+/* Activation-aware MXFP4 (additive, the ABI number stays): the per-input-channel scale
+ * search of awq_act_* scored on the MXFP4 grid, and the winner's one-pass quantize.  w [rows, K] of dtype
+ * D (bf16 / fp16 / fp32), K % 32 == 0; table and rtable fp32 [n_grid, K] as awq_act_scale_table and
+ * awq_act_recip_table make them (rtable may be NULL: IEEE divisions, the same bits); x_sq fp32 [K].
+ * awq_act_search_losses_mxfp4, candidate i, every block of 32 along a row, every operation one fp32
+ * operation rounded on its own:
+ *   w' = RN_D(w * s_i[k])                                  (the bits of awq_apply_input_scale)
+ *   the block's scale byte e and rounded magnitudes m of w' exactly as awq_quantize_mxfp4 takes them for
+ *       dtype D under `rule` (the "mse" sums in its order)
+ *   dq = +-m 2^(e - 127) (exact; beyond fp32's range inf); a block with e = 255: dq = NaN
+ *   d = RN_f32(dq / s_i[k]) - w;  c = x_sq[k] * (d * d)
+ *   block loss: four runs of 8 elements, each summed in order from +0, then (p0 + p1) + (p2 + p3)
+ *       -> part[i * part_stride + row * (K / 32) + block]
+ * awq_act_search_select then serves unchanged, with the blocks in the groups' place.  The kernel stages 32
+ * candidates at a time: the weight is read once for n_grid <= 32, once per chunk of 32 beyond (up to 8 times).
+ * awq_quantize_mxfp4_scaled: the codes and scales of awq_apply_input_scale into a copy followed by
+ * awq_quantize_mxfp4 of the copy, byte for byte, without the copy; col_scale fp32 [K].
+ * Checked in this order, nothing launched on a failure: awq_quantize_mxfp4's shape and dtype checks; the
+ * rule; n_grid outside [1, AWQ_ACT_MAX_GRID] (AWQ_EINVAL); rows K == 0: AWQ_OK, no pointer is looked at;
+ * part_stride below rows K / 32 (AWQ_EINVAL); K above 256 (2^31 - 1) (AWQ_EUNSUPPORTED); a NULL pointer other
+ * than rtable; w, table, rtable, x_sq or col_scale not 16-B aligned, part, codes or scales not 4-B
+ * (AWQ_EINVAL).  Launches go to the caller's stream; no allocation, no synchronisation. */
+int awq_act_search_losses_mxfp4(const void* w, int dtype, int64_t rows, int64_t K, int rule, const float* table,
+                                const float* rtable, int n_grid, const float* x_sq, float* part,
+                                int64_t part_stride, void* stream);
+int awq_quantize_mxfp4_scaled(const void* w, int dtype, int64_t rows, int64_t K, int rule, const float* col_scale,
+                              uint8_t* codes, uint8_t* scales, void* stream);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
