@@ -170,6 +170,7 @@ SIGNATURES = {
     "awq_gptq_round_block_mxfp4": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _I64, _P, _P, _P, _P]),
     "awq_act_search_losses_mxfp4": (_I32, [_P, _I32, _I64, _I64, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
     "awq_quantize_mxfp4_scaled": (_I32, [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _P]),
+    "awq_mxfp4_gemm": (_I32, [_P, _P, _I64, _P, _P, _I64, _I64, _P, _I32, _P, _I32, _P]),
 }
 
 _lib = None
@@ -1103,3 +1104,21 @@ def quantize_mxfp4_scaled(w: torch.Tensor, s: torch.Tensor, rule: str, codes: to
     check(load_library().awq_quantize_mxfp4_scaled(ptr(w), AWQ_DTYPE.get(w.dtype, -1), rows, K, MXFP4_RULES[rule],
                                                    ptr(s), ptr(codes), ptr(scales), _stream(w)),
           "awq_quantize_mxfp4_scaled")
+
+
+def mxfp4_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
+               out: torch.Tensor, bias: Optional[torch.Tensor] = None) -> None:
+    """awq_mxfp4_gemm: out [T, N] (bf16 / fp16 / fp32, contiguous) = a w^T (+ bias [N]) of two MXFP4 operands,
+    a [T, K] and w [N, K] as codes / scales pairs, on the scaled matrix instruction."""
+    T, N = out.shape
+    K = a_codes.shape[1] * 2
+    if K % 32 == 0:
+        _mxfp4_pair(a_codes, a_scales, T, K)
+        _mxfp4_pair(w_codes, w_scales, N, K)
+    if not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("mxfp4_gemm: out must be a contiguous device tensor")
+    if bias is not None and (tuple(bias.shape) != (N,) or not bias.is_contiguous() or bias.device != out.device):
+        raise ValueError(f"mxfp4_gemm: bias must be a contiguous [{N}] tensor on {out.device}")
+    check(load_library().awq_mxfp4_gemm(ptr(a_codes), ptr(a_scales), T, ptr(w_codes), ptr(w_scales), N, K, ptr(bias),
+                                        AWQ_DTYPE.get(bias.dtype, -1) if bias is not None else 0, ptr(out),
+                                        AWQ_DTYPE.get(out.dtype, -1), _stream(out)), "awq_mxfp4_gemm")

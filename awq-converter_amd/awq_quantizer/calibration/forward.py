@@ -245,6 +245,7 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
     n, seq = input_ids.shape
     spans, fused = plan_micro_batches(n, seq, batch_tokens)
     H, nh, nkv, hd = cfg.hidden_size, cfg.num_heads, cfg.num_kv_heads, cfg.head_dim
+    linear = getattr(ops, "linear", F.linear)   # the four decoder linears; evaluation may run them in MXFP4
 
     def fetch(names):
         return {k: loader.read(index[k]) for k in names}
@@ -305,7 +306,7 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
 
                 hn = ops.rmsnorm(x, w["input_layernorm.weight"], cfg.eps, accs["attn_in"], fused)
                 take("attn_in", hn)
-                qkv = F.linear(hn, w_qkv, b_qkv).view(m, seq, nh + 2 * nkv, hd).transpose(1, 2)
+                qkv = linear(hn, w_qkv, b_qkv).view(m, seq, nh + 2 * nkv, hd).transpose(1, 2)
                 q, k, v = qkv[:, :nh], qkv[:, nh:nh + nkv], qkv[:, nh + nkv:]
                 q = q * cos + rotate_half(q) * sin
                 k = k * cos + rotate_half(k) * sin
@@ -316,13 +317,13 @@ def run_decoder(loader, cfg: DecoderConfig, input_ids: torch.Tensor, dtype: torc
                 att = att.transpose(1, 2).reshape(m * seq, nh * hd)
                 ops.accum(att, accs["attn_out"])
                 take("attn_out", att)
-                x += F.linear(att, w["self_attn.o_proj.weight"], w.get("self_attn.o_proj.bias"))
+                x += linear(att, w["self_attn.o_proj.weight"], w.get("self_attn.o_proj.bias"))
                 hn = ops.rmsnorm(x, w["post_attention_layernorm.weight"], cfg.eps, accs["mlp_in"], fused)
                 take("mlp_in", hn)
-                gu = F.linear(hn, w_gu, b_gu)                     # [T, 2 * inter]: gate | up
+                gu = linear(hn, w_gu, b_gu)                     # [T, 2 * inter]: gate | up
                 act = ops.swiglu(gu[:, :inter], gu[:, inter:], accs["mlp_out"], fused)
                 take("mlp_out", act)
-                x += F.linear(act, w["mlp.down_proj.weight"], w.get("mlp.down_proj.bias"))
+                x += linear(act, w["mlp.down_proj.weight"], w.get("mlp.down_proj.bias"))
             for group, acc in accs.items():
                 if acc is not None:
                     publish(acc, lin[group])

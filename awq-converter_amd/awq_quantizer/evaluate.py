@@ -23,6 +23,9 @@ from typing import List, Optional
 from .utils.logger import get_logger
 
 
+MXFP4_ACT_NEEDS = "--mxfp4_activations needs --quantized_dir to be an MXFP4 directory (--output_format mxfp4)"
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="awq_quantizer.evaluate",
                                 description="Perplexity, KL divergence and top-1 agreement of a written checkpoint")
@@ -37,6 +40,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--compute_dtype", type=str, default=None, choices=["bfloat16", "float16", "float32"],
                    help="Dtype of the forward (default: the checkpoint's)")
     p.add_argument("--batch_tokens", type=int, default=8192, help="Tokens per micro-batch and per head chunk")
+    p.add_argument("--mxfp4_activations", action="store_true",
+                   help="Run the quantized model's decoder linears with MXFP4 activations too (W4A4, the scaled "
+                        "matrix instruction); needs an MXFP4 --quantized_dir")
     p.add_argument("--report", type=str, default=None, help="Also write the aggregates and the arguments (JSON)")
     p.add_argument("--max_ppl_ratio", type=float, default=None, help="Return 1 when ppl_q / ppl_ref exceeds this")
     p.add_argument("--max_kl", type=float, default=None, help="Return 1 when the mean KL divergence exceeds this")
@@ -59,6 +65,12 @@ def check_args(args) -> Optional[str]:
         return f"--model_id: {args.model_id} is not a directory"
     if args.quantized_dir is not None and not os.path.isdir(args.quantized_dir):
         return f"--quantized_dir: {args.quantized_dir} is not a directory"
+    if getattr(args, "mxfp4_activations", False):
+        from .verify import is_mxfp4_dir
+        if args.quantized_dir is None or not is_mxfp4_dir(args.quantized_dir):
+            return MXFP4_ACT_NEEDS
+        if args.compute_dtype == "float16":
+            return "--mxfp4_activations runs in bfloat16 or float32, not float16"
     return None
 
 
@@ -98,7 +110,8 @@ def main(argv: Optional[List[str]] = None, evaluate_fn=None) -> int:
         if evaluate_fn is None:
             from .evaluation import evaluate_model as evaluate_fn
         result = evaluate_fn(args.model_id, ids, quantized_dir=args.quantized_dir, compute_dtype=args.compute_dtype,
-                             batch_tokens=args.batch_tokens, device=args.device, logger=logger)
+                             batch_tokens=args.batch_tokens, device=args.device, logger=logger,
+                             **({"mxfp4_activations": True} if args.mxfp4_activations else {}))
     except Exception as e:  # noqa: BLE001
         logger.error(f"Evaluation failed: {e}")
         return 1

@@ -21,10 +21,11 @@ import torch.nn.functional as F
 
 from ..calibration import check_input_ids, resolve_dtype
 from ..calibration.forward import HipOps, parse_config, read_config, run_decoder
+from ..evaluate import MXFP4_ACT_NEEDS
 from .checkpoint import DeviceDequant, QuantizedCheckpoint
 
-__all__ = ["compare_logits", "evaluate_model", "aggregate", "shifted_targets", "HipEvalOps", "QuantizedCheckpoint",
-           "DeviceDequant"]
+__all__ = ["compare_logits", "evaluate_model", "aggregate", "shifted_targets", "HipEvalOps", "Mxfp4LinearOps",
+           "QuantizedCheckpoint", "DeviceDequant"]
 
 def shifted_targets(input_ids: torch.Tensor) -> torch.Tensor:
     """[n, seq] ids -> int64 [n * seq]: the next token of the same sequence; -1 (not scored) at
@@ -106,6 +107,27 @@ class HipEvalOps(HipOps):
         return _device_compare(ref, q, targets)
 
 
+class Mxfp4LinearOps:
+    """`ops` with the four decoder linears in MXFP4 on both sides (W4A4): the activation is
+    block-quantized under the floor rule, the dense weight the loader dequantized is quantized again under the
+    floor rule (exact: its blocks already lie on the grid that rule picks), and the product runs through
+    awq_mxfp4_gemm.  Nothing is cached: the weight pass is one streaming read against a T x N x K product.  A
+    linear whose in_features % 32 != 0 stays dense."""
+
+    def __init__(self, ops, device):
+        from ..quantization.awq import AWQQuantizer
+        self._ops = ops
+        self.q = AWQQuantizer(device=str(device), logger_name="awq_evaluate_quantizer", logger_level="WARNING")
+
+    def __getattr__(self, name):
+        return getattr(self._ops, name)
+
+    def linear(self, x, w, b=None):
+        if w.shape[1] % 32 != 0:
+            return F.linear(x, w, b)
+        return self.q.mxfp4_linear(x, self.q.quantize_mxfp4(w, "floor"), b, "floor")
+
+
 def _tail(cfg, loaders, hiddens, targets, dtype, device, ops, batch_tokens) -> Dict[str, torch.Tensor]:
     """final norm -> head -> comparison, per chunk of <= batch_tokens tokens.  loaders / hiddens:
     the source's, then (optionally) the quantized model's."""
@@ -129,14 +151,17 @@ def _tail(cfg, loaders, hiddens, targets, dtype, device, ops, batch_tokens) -> D
 
 def evaluate_model(model_dir: str, input_ids, quantized_dir: Optional[str] = None, compute_dtype=None,
                    batch_tokens: int = 8192, device="cuda", logger=None, ops=None, dequant=None,
-                   per_token: Optional[Dict[str, torch.Tensor]] = None) -> dict:
+                   per_token: Optional[Dict[str, torch.Tensor]] = None, mxfp4_activations: bool = False) -> dict:
     """Perplexity of the model in model_dir on input_ids [n, seq] (targets: the next token of the
     same sequence; every sequence's last position is not scored) and, with quantized_dir (any
     directory main wrote), of the quantized model, with KL(source || quantized) and the top-1
     agreement over every position.  Returns n_tokens_scored, n_positions, nll_ref_sum, ppl_ref,
     top1_accuracy_ref, nonfinite_rows, and with quantized_dir nll_q_sum, ppl_q, ppl_ratio, kl_mean,
     kl_max, top1_agreement, top1_accuracy_q.  per_token, when a dict, receives the per-token
-    tensors (CPU).  compute_dtype: the checkpoint's by default."""
+    tensors (CPU).  compute_dtype: the checkpoint's by default.  mxfp4_activations (quantized_dir an
+    MXFP4 directory, bf16 or fp32 compute, the HIP ops): the quantized model's decoder linears run with both
+    operands in MXFP4 (Mxfp4LinearOps); the source's forward and both heads stay dense, and the result says so
+    ("activations": "mxfp4", "head": "dense")."""
     from ..model_loading.safetensors_loader import SafetensorsLoader
     ids = check_input_ids(input_ids)
     if batch_tokens <= 0:
@@ -153,15 +178,20 @@ def evaluate_model(model_dir: str, input_ids, quantized_dir: Optional[str] = Non
         dtype = resolve_dtype(compute_dtype, embed.dtype if embed is not None else None)
         if isinstance(ops, HipOps) and dtype == torch.float64:
             raise ValueError("compute_dtype float64: the kernels take bfloat16 / float16 / float32")
+        if mxfp4_activations and (not isinstance(ops, HipOps) or dtype not in (torch.bfloat16, torch.float32)):
+            raise ValueError("mxfp4_activations needs the HIP ops and bfloat16 or float32 compute")
         loaders = [loader]
         if quantized_dir is not None:
             qloader = QuantizedCheckpoint(loader, quantized_dir, dequant or DeviceDequant(device))
             loaders.append(qloader)
+        if mxfp4_activations and (qloader is None or qloader.format != "mxfp4"):
+            raise ValueError(MXFP4_ACT_NEEDS)
         hiddens = []
         with torch.no_grad():
             for ld in loaders:
                 got: Dict[str, torch.Tensor] = {}
-                run_decoder(ld, cfg, ids, dtype, device, ops, batch_tokens=batch_tokens, logger=logger, stats=False,
+                ld_ops = Mxfp4LinearOps(ops, device) if mxfp4_activations and ld is qloader else ops
+                run_decoder(ld, cfg, ids, dtype, device, ld_ops, batch_tokens=batch_tokens, logger=logger, stats=False,
                             hidden_out=got)
                 hiddens.append(got["hidden"])
             targets = shifted_targets(ids).to(device)
@@ -169,7 +199,10 @@ def evaluate_model(model_dir: str, input_ids, quantized_dir: Optional[str] = Non
         if per_token is not None:
             per_token.update({k: v.cpu() for k, v in per.items()})
             per_token["targets"] = targets.cpu()
-        return aggregate(per, targets)
+        out = aggregate(per, targets)
+        if mxfp4_activations:
+            out.update(activations="mxfp4", head="dense")
+        return out
     finally:
         if qloader is not None:
             qloader.close()

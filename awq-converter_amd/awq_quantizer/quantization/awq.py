@@ -685,6 +685,15 @@ class AWQQuantizer:
         from .mxfp4 import dequantize_mxfp4
         return dequantize_mxfp4(self, result, dtype)
 
+    def mxfp4_linear(self, x: torch.Tensor, result: Dict[str, torch.Tensor], bias: Optional[torch.Tensor] = None,
+                     act_rule: str = "floor", dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """F.linear(x, w, bias) with both operands in MXFP4 (W4A4; mxfp4.py; include/awq_hip.h awq_mxfp4_gemm;
+        DESIGN.md §5.25): x [T, K] is block-quantized along K under act_rule, the product with the
+        quantize_mxfp4 result runs on the scaled matrix instruction with fp32 accumulation, and [T, N] of
+        dtype (x's by default) comes back on the compute device."""
+        from .mxfp4 import mxfp4_linear
+        return mxfp4_linear(self, x, result, bias, act_rule, dtype)
+
     def hadamard_transform(self, x: torch.Tensor, dim: int, *, length: Optional[int] = None,
                            pre: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The orthonormal Hadamard transform of x along dim (0 or -1), in segments of `length`

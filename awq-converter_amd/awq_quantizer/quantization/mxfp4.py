@@ -76,6 +76,32 @@ def dequantize_mxfp4(q, result: dict, dtype: torch.dtype = torch.float32) -> tor
     return out
 
 
+def mxfp4_matmul(q, a_result: dict, w_result: dict, bias=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """a [T, K] times w [N, K] transposed, both MXFP4 results, (+ bias [N]) -> [T, N] of `dtype` on the
+    compute device, through awq_mxfp4_gemm (both operands FP4 on the scaled matrix instruction, fp32
+    accumulation, one rounding)."""
+    if dtype not in DTYPES:
+        raise ValueError(f"mxfp4_matmul writes bf16 / fp16 / fp32, got {dtype}")
+    a_codes, a_scales, T, K = _parts(q, a_result)
+    w_codes, w_scales, N, Kw = _parts(q, w_result)
+    if K != Kw:
+        raise ValueError(f"mxfp4_matmul: a is [{T}, {K}], w is [{N}, {Kw}]: the inner sizes differ")
+    if bias is not None:
+        if bias.dtype not in DTYPES or tuple(bias.shape) != (N,):
+            raise ValueError(f"mxfp4_matmul: bias must be a bf16 / fp16 / fp32 [{N}], got {bias.dtype} "
+                             f"{tuple(bias.shape)}")
+        bias = bias.to(a_codes.device).contiguous()
+    out = torch.empty((T, N), dtype=dtype, device=a_codes.device)
+    _hip.mxfp4_gemm(a_codes, a_scales, w_codes, w_scales, out, bias)
+    return out
+
+
+def mxfp4_linear(q, x: torch.Tensor, w_result: dict, bias=None, act_rule: str = "floor", dtype=None) -> torch.Tensor:
+    """F.linear with both operands in MXFP4 (W4A4): x [T, K] is block-quantized along K under `act_rule`
+    (awq_quantize_mxfp4), then mxfp4_matmul with the weight result.  The output dtype defaults to x's."""
+    return mxfp4_matmul(q, quantize_mxfp4(q, x, act_rule), w_result, bias, x.dtype if dtype is None else dtype)
+
+
 def quantization_error(q, tensor: torch.Tensor, result: dict, per_group: bool = False, samples=None) -> dict:
     """AWQQuantizer.quantization_error for an MXFP4 result: the keys of the integer formats' report
     without samples (error_report, plus input_scaled = False), from one pass of awq_mxfp4_error."""

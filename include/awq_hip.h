@@ -1110,6 +1110,26 @@ int awq_act_search_losses_mxfp4(const void* w, int dtype, int64_t rows, int64_t 
 int awq_quantize_mxfp4_scaled(const void* w, int dtype, int64_t rows, int64_t K, int rule, const float* col_scale,
                               uint8_t* codes, uint8_t* scales, void* stream);
 
+/* MXFP4 x MXFP4 product on the scaled matrix instruction (additive, the ABI number stays):
+ *   out[t, n] = sum_k a[t, k] * w[n, k] (+ bias[n]),  t < T, n < N, K % 32 == 0.
+ * Both operands as awq_quantize_mxfp4 writes them: a_codes [T, K / 2] and w_codes [N, K / 2] (the even element
+ * in the low nibble), a_scales [T, K / 32] and w_scales [N, K / 32] (E8M0).  out [T, N] contiguous, bf16 / fp16 /
+ * fp32; bias [N] of bias_dtype (bf16 / fp16 / fp32) or NULL (bias_dtype is then not looked at).
+ * Every product mag_a mag_w 2^(ea + ew - 254) is exact.  One output element: acc = +0; for every run of 64
+ * consecutive k, in increasing order, ONE v_mfma_scale_f32_32x32x64_f8f6f4 adds the run's 64 products to acc
+ * in fp32 (inside the instruction the order is the hardware's; a K % 64 == 32 tail adds 32 products and 32
+ * zeros); then acc + bias[n] in fp32; one rounding to nearest even into out_dtype.  A scale byte 255 anywhere
+ * in row t of A or row n of W makes out[t, n] NaN.  Results whose exact value or partial sums leave fp32's
+ * normal range are not pinned.
+ * Checked in this order, nothing launched and out untouched on a failure: T, N or K <= 0; K % 32 != 0; an
+ * out_dtype, or with a bias a bias_dtype, that is not bf16 / fp16 / fp32 (AWQ_EINVAL); a product of two of
+ * T, N, K above 2^60, or more than 2^31 - 1 tiles of 128 x 128 (AWQ_EUNSUPPORTED); a NULL pointer other than
+ * bias; a_codes or w_codes not 16-B aligned, out or bias not aligned to its element (AWQ_EINVAL).  Every index
+ * is 64-bit.  The launch goes to the caller's stream; no allocation, no synchronisation, no global state. */
+int awq_mxfp4_gemm(const uint8_t* a_codes, const uint8_t* a_scales, int64_t T, const uint8_t* w_codes,
+                   const uint8_t* w_scales, int64_t N, int64_t K, const void* bias, int bias_dtype, void* out,
+                   int out_dtype, void* stream);
+
 /* Device self-test (diagnostics).  which = 0: the fast reciprocal used by the streaming
  * kernel against IEEE 1/s over every bf16 s >= RN_bf16(1e-10); which = 1: the loss kernel's
  * Markstein quotient against the IEEE division for every s in [1, 2) and every positive
